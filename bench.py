@@ -10,6 +10,11 @@ Multi-GPU (driver runs): python -m torch.distributed.run --nnodes=1 \
     --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
     bench.py --gpus N --steps K --warmup W
 
+A plain run sets up, warms up, times exactly K steps and prints one JSON
+result line. --full adds the secondary measurement (p50 single-step
+latency probes, config.p50_step_ms). --dump-outputs DIR writes the
+parameters the last timed step produced as DIR/<name>.npy (float32).
+
 Engines (--engine): persistent (default; S steps per kernel launch at
 world 1, falls back to fused when a communicator exists), fused (one
 fused kernel + collective + fused SGD per step), graph (fused step
@@ -47,7 +52,18 @@ def parse_args():
     p.add_argument("--batch", type=int, default=32, help="batch per rank")
     p.add_argument("--lr", type=float, default=1e-3)
     p.add_argument("--dataset", type=int, default=2048)
-    p.add_argument("--p50-probes", type=int, default=64)
+    p.add_argument("--p50-probes", type=int, default=64,
+                   help="synchronized single-step latency probes "
+                        "(run only with --full)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements (the p50 "
+                        "single-step latency probes); a plain run only "
+                        "sets up, warms up, times --steps steps and "
+                        "prints the result line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the timed path "
+                        "produced in its last step (the trained "
+                        "parameters) as DIR/<name>.npy in float32")
     p.add_argument("--dtype", choices=["fp32", "bf16"], default="fp32",
                    help="compute dtype (fp32 = the reference's; bf16 = "
                         "BASELINE.json config 2)")
@@ -195,7 +211,21 @@ def drive_shard_bound(data, spe, batch, eb, bind, step_shard, start, n):
         step_shard((e - b * eb) * spe + i)
 
 
+def dump_outputs(out_dir, model):
+    """Write the timed path's result -- the model parameters as the last
+    timed step left them -- as <out_dir>/<name>.npy (float32; the toy
+    model is 21 values). Inputs and init are seeded, so equal arguments
+    give comparable files from run to run and build to build."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, p in model.named_parameters():
+        arr = p.detach().to(device="cpu", dtype=torch.float32).numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
 def build_engine(kind, comm, lr, device, dtype=torch.float32, use_mse=True):
+    """Returns (step, flush, engine object or None, model)."""
     from mi355x_ddp.engine import (GraphedToyStep, PersistentToyStep,
                                    ToyFusedStep)
     from mi355x_ddp.models import toy_model
@@ -220,14 +250,15 @@ def build_engine(kind, comm, lr, device, dtype=torch.float32, use_mse=True):
             from mi355x_ddp.engine import GraphedAutogradStep
             gs = GraphedAutogradStep(engine, loss_fn, opt,
                                      finalize=engine.finalize_backward)
-            return gs.step, gs.flush, gs  # shard-bound protocol supported
+            # shard-bound protocol supported
+            return gs.step, gs.flush, gs, model
 
         def step(x, t):
             loss = loss_fn(engine(x), t)
             loss.backward()
             engine.finalize_backward()
             opt.step()
-        return step, noflush, None
+        return step, noflush, None, model
 
     if (kind == "persistent" and comm is not None
             and getattr(comm, "_mesh", None) is None):
@@ -237,7 +268,7 @@ def build_engine(kind, comm, lr, device, dtype=torch.float32, use_mse=True):
     eng = cls(model, comm=comm, lr=lr, use_mse=use_mse)
     if comm is not None:
         eng.reducer.broadcast_params(root=0)
-    return eng.step, getattr(eng, "flush", noflush), eng
+    return eng.step, getattr(eng, "flush", noflush), eng, model
 
 
 def main():
@@ -287,12 +318,13 @@ def main():
             f"--dataset {args.dataset} yields {data.per_rank} samples/rank "
             f"at world {world}: smaller than one --batch {args.batch}")
 
-    step_fn = flush_fn = engine_obj = None
+    step_fn = flush_fn = engine_obj = model = None
     eng_bind = eng_step_shard = None
 
     def make_engine():
-        nonlocal step_fn, flush_fn, engine_obj, eng_bind, eng_step_shard
-        step_fn, flush_fn, engine_obj = build_engine(
+        nonlocal step_fn, flush_fn, engine_obj, model
+        nonlocal eng_bind, eng_step_shard
+        step_fn, flush_fn, engine_obj, model = build_engine(
             args.engine if use_cuda else "autograd", comm, args.lr, device,
             dtype if use_cuda else torch.float32, use_mse=args.loss == "mse")
         # shard-bound fast path: bind each epoch's shard once, then drive
@@ -384,11 +416,15 @@ def main():
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
         elapsed = float(e)
 
-    # -- p50 step time (instrumented separately, outside the headline
-    #    region: per-step sync would serialize the pipeline) --------------
+    # -- outputs of the timed path, before anything else trains further --
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model)
+
+    # -- p50 step time (--full only; instrumented separately, outside the
+    #    headline region: per-step sync would serialize the pipeline) -----
     import statistics
     probes = []
-    for s in range(args.p50_probes):
+    for s in range(args.p50_probes if args.full else 0):
         x, t = data.batch_for(s)
         if use_cuda:
             torch.cuda.synchronize()

@@ -11,10 +11,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_json_contract(tmp_path):
     out = subprocess.run(
         [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "30",
-         "--warmup", "5", "--p50-probes", "4"],
+         "--warmup", "5", "--full", "--p50-probes", "4"],
         cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     r = json.loads(out.stdout.strip().splitlines()[-1])
+    assert r["config"]["p50_step_ms"] > 0  # --full runs the latency probes
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup",
                 "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
                 "dtype", "data", "config"):
@@ -29,6 +30,37 @@ def test_bench_json_contract(tmp_path):
         assert key in cfg, key
     assert cfg["model"] == "Linear(20,1)"
     assert r["value"] > 0 and r["ms_per_step"] > 0
+
+
+def _plain_run_with_dump(out_dir):
+    out = subprocess.run(
+        [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1",
+         "--steps", "30", "--warmup", "5", "--dump-outputs", str(out_dir)],
+        cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    return json.loads(out.stdout.strip().splitlines()[-1])
+
+
+def test_bench_plain_run_dumps_reproducible_outputs(tmp_path):
+    # a plain run (no --full) skips the latency probes, and --dump-outputs
+    # writes the trained parameters as float32 .npy files that are
+    # identical from run to run with the same arguments
+    import numpy as np
+
+    r = _plain_run_with_dump(tmp_path / "a")
+    assert r["steps"] == 30 and r["ms_per_step"] > 0
+    assert r["config"]["p50_step_ms"] is None
+    _plain_run_with_dump(tmp_path / "b")
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["bias.npy", "weight.npy"]
+    assert sorted(os.listdir(tmp_path / "b")) == names
+    for name in names:
+        a = np.load(tmp_path / "a" / name)
+        b = np.load(tmp_path / "b" / name)
+        assert a.dtype == np.float32 and np.isfinite(a).all()
+        assert a.shape == b.shape and np.array_equal(a, b)
+    assert np.load(tmp_path / "a" / "weight.npy").shape == (1, 20)
+    assert np.load(tmp_path / "a" / "bias.npy").shape == (1,)
 
 
 def test_bench_defaults_finish_quickly():
@@ -213,7 +245,7 @@ def test_bench_world2_gloo_driver_form():
          "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
          "--master-port", str(port), os.path.join(ROOT, "bench.py"),
          "--gpus", "2", "--steps", "20", "--warmup", "4",
-         "--p50-probes", "2"],
+         "--full", "--p50-probes", "2"],
         cwd=ROOT, capture_output=True, text=True, timeout=420)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]

@@ -151,7 +151,7 @@ def test_bench_single_gpu_json():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run(
         [sys.executable, os.path.join(root, "bench.py"), "--steps", "50",
-         "--warmup", "10", "--p50-probes", "8"],
+         "--warmup", "10", "--full", "--p50-probes", "8"],
         cwd=root, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     line = out.stdout.strip().splitlines()[-1]

@@ -79,11 +79,14 @@ def test_block_bound_run_matches_per_epoch(dtype):
 def test_bench_epoch_block_json():
     """bench.py default path picks an epoch block > 1 and reports it."""
     import json
+    import os
     import subprocess
     import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run(
-        [sys.executable, "bench.py", "--steps", "600", "--warmup", "100"],
-        capture_output=True, text=True, timeout=300, check=True)
+        [sys.executable, os.path.join(root, "bench.py"), "--steps", "600",
+         "--warmup", "100"],
+        cwd=root, capture_output=True, text=True, timeout=300, check=True)
     line = json.loads(out.stdout.strip().splitlines()[-1])
     assert line["config"]["epoch_block"] > 1
     assert line["config"]["engine"] == "persistent"
