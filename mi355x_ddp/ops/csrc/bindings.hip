@@ -66,6 +66,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("param_flat"), py::arg("loss_out"), py::arg("use_mse") = true,
         py::arg("w_off") = 0, py::arg("b_off") = 0, py::arg("lr") = 0.0,
         py::arg("batch") = 32);
+  // fp32 (32|64, 20) multi-step kernel selector: "chain" (default) | "mfma"
+  m.def("set_toy_multistep_impl", &mi355x::set_toy_multistep_impl,
+        py::arg("name"));
+  m.def("get_toy_multistep_impl", &mi355x::get_toy_multistep_impl);
+  m.def("set_toy_multistep_chain_depth",
+        &mi355x::set_toy_multistep_chain_depth, py::arg("depth"));
 
   py::class_<mi355x::P2pMesh>(m, "P2pMesh")
       .def(py::init<int, int, int>(), py::arg("rank"), py::arg("world"),

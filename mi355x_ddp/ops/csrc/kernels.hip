@@ -15,7 +15,14 @@
 // xf32/TF32 exists on gfx950 — cdna_hip_programming.md §3) and
 // `v_mfma_f32_16x16x32_bf16` for bf16; the toy shapes are single-wave
 // and latency-bound, so the MFMA path buys kernel-count and issue-slot
-// economy, not FLOPs.
+// economy, not FLOPs. The one exception is the fp32
+// world-1 multi-step fast path (batch 32/64, K 20): `k_toy_multistep_chain`
+// runs the same k-ordered fmaf chains the f32 MFMA evaluates, bit for bit,
+// on the vector ALU — one row (forward) / one column (backward) per lane,
+// cross-lane hand-offs by v_readlane broadcast, no LDS and no barrier —
+// because those MFMA tiles discard 15/16 of their work on the serial
+// critical path (3.6x faster in kernel, profiles r03a). The MFMA spec
+// kernel stays selectable (set_toy_multistep_impl / MI355X_TOY_MULTISTEP).
 //
 // Beyond parity (design notes in docs/KERNELS.md): the multi-step
 // trainers (`k_toy_multistep_spec`, `k_toy_multistep_bf16w`) run S
@@ -30,6 +37,11 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include <c10/hip/HIPStream.h>
+
+#include <atomic>
+#include <cstdint>
+#include <cstdlib>
+#include <string>
 
 #include "ops.h"
 #include "p2p_mesh.h"
@@ -1672,6 +1684,230 @@ k_toy_multistep_spec(const T* __restrict__ X, const T* __restrict__ Tg,
   if (lane == 0 && loss_out) *loss_out = use_mse ? loss_last / (float)B_ : 0.f;
 }
 
+// ---------------------------------------------------------------------------
+// Lane-parallel fmaf-chain form of the fp32 multi-step trainer (the world-1
+// default for batch 32/64, K 20). The f32-input MFMA result is bit-for-bit
+// a k-ordered f32 fmaf chain with one rounding per product
+// (cdna_hip_programming.md §3), and the spec kernel above uses ONE column
+// (forward) / ONE row (backward) of each 16x16 MFMA tile — so the same
+// bits come off the vector ALU with only the useful work and no LDS:
+//   forward   lane m owns row m of X:  y = fmaf(x[m][k], w[k], y), k = 0..K-1
+//   loss grad all rows at once:        dy = ((y + b) - t) * (2/B)
+//   backward  lane k owns column k:    g = fmaf(dy[i], x[i][k], g), i = 0..B-1
+//             lane K_ multiplies by a constant 1 (the db column)
+//   update    w[k] stays in lane k's register for the whole launch
+//             (bias in lane K_): w -= lr * g
+// B_ = 8x4 (or 16x4) and K_ = 5x4 fill the MFMA k-groups exactly, so the
+// MFMA chain order is the plain index order with no padding terms. The two
+// cross-lane hand-offs are broadcasts of wave-uniform values (w[k] to the
+// row lanes, dy[i] to the column lanes): v_readlane_b32 with a constant
+// lane puts each in an SGPR the v_fma reads directly — no LDS, no barrier.
+// Operands stream through a ring of D register sets (distance-D prefetch,
+// unrolled by D like the bf16 kernel's setA/setB): rows as 16-byte loads
+// when VEC4 (tile base 16-byte aligned; rows are 80 B), columns as dwords.
+// Loads are unconditional with clamped addresses and never pass tile S-1.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ float lane_bcast(float v, int src_lane) {
+  return __int_as_float(
+      __builtin_amdgcn_readlane(__float_as_int(v), src_lane));
+}
+
+// A tile of ones with the X tile's row pitch: the db lane (and the idle
+// lanes above it) stream their backward operand from here with the same
+// immediate offsets as a real column, so the constant-1 column costs no
+// per-term select on the chain. Deliberately not `const`: a const device
+// variable lands in the constant address space, and a pointer select
+// between it and the global X pointer degrades every column load to a FLAT
+// load, whose out-of-order return forces full vmcnt(0) drains.
+template <int N>
+struct OnesTile {
+  float v[N];
+  constexpr OnesTile() : v() {
+    for (int i = 0; i < N; ++i) v[i] = 1.f;
+  }
+};
+__device__ OnesTile<64 * 20> k_ones_tile{};
+
+template <int B_, int K_, int D, bool VEC4>
+__global__ void __launch_bounds__(64, 1)
+k_toy_multistep_chain(const float* __restrict__ X,
+                      const float* __restrict__ Tg,
+                      float* __restrict__ param, float* __restrict__ loss_out,
+                      int S, int use_mse, int w_off, int b_off, float lr) {
+  static_assert((B_ == 32 || B_ == 64) && K_ == 20 && D >= 1,
+                "chain path: B in {32, 64}, K = 20 (k_ones_tile pitch)");
+  const int lane = threadIdx.x;
+  const int mr = lane & (B_ - 1);  // row owned in the forward
+  const float inv2B = 2.f / (float)B_;
+  // w[k] in lane k, bias in lane K_ (lanes above hold an unused copy)
+  float wv = param[(lane < K_) ? w_off + lane : b_off];
+  // backward operand stream: column `lane` of X for lanes < K_, advancing
+  // one tile per step; the ones tile (never advancing) for lane K_ and up
+  const float* colp = (lane < K_) ? X + lane : k_ones_tile.v;
+  const size_t cstep = (lane < K_) ? (size_t)(B_ * K_) : 0;
+
+  struct CSet {
+    float xr[K_];  // fwd: X[mr][0..K_)
+    float xc[B_];  // bwd: X[0..B_)[lane] (ones on the db lane)
+    float t;       // target of row mr
+  };
+  CSet ring[D];
+
+  // Unconditional loads; the step index is clamped to the last tile, so
+  // the D prefetches past the end re-read tile S-1 and nothing beyond it.
+  auto prefetch = [&](CSet& R, int s_raw) {
+    const int s = (s_raw < S) ? s_raw : S - 1;
+    const float* rowp = X + (size_t)s * (B_ * K_) + mr * K_;
+    if constexpr (VEC4) {
+#pragma unroll
+      for (int j = 0; j < K_ / 4; ++j) {
+        const float4 v = *reinterpret_cast<const float4*>(rowp + 4 * j);
+        R.xr[4 * j + 0] = v.x;
+        R.xr[4 * j + 1] = v.y;
+        R.xr[4 * j + 2] = v.z;
+        R.xr[4 * j + 3] = v.w;
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < K_; ++k) R.xr[k] = rowp[k];
+    }
+    R.t = Tg[(size_t)s * B_ + mr];
+    const float* cp = colp + (size_t)s * cstep;
+#pragma unroll
+    for (int i = 0; i < B_; ++i) R.xc[i] = cp[i * K_];
+  };
+
+  float d_last = 0.f;
+  auto body = [&](CSet& R, int s) {
+    // ---- forward: y = X @ w, k-ordered chain from +0 ----
+    float wk[K_ + 1];
+#pragma unroll
+    for (int k = 0; k <= K_; ++k) wk[k] = lane_bcast(wv, k);
+    float y = 0.f;
+#pragma unroll
+    for (int k = 0; k < K_; ++k) y = __builtin_fmaf(R.xr[k], wk[k], y);
+    const float bterm = wk[K_];
+
+    // ---- loss grad: one row per lane ----
+    const float d = y + bterm - R.t;
+    const float dy = use_mse ? d * inv2B : 0.f;
+    d_last = d;
+
+    // ---- backward: dw_k = sum_i dY_i X[i,k]; db on the ones lane ----
+    float dyi[B_];
+#pragma unroll
+    for (int i = 0; i < B_; ++i) dyi[i] = lane_bcast(dy, i);
+    float g = 0.f;
+#pragma unroll
+    for (int i = 0; i < B_; ++i) g = __builtin_fmaf(dyi[i], R.xc[i], g);
+
+    // this set's regs are dead from here: refill them for step s + D
+    prefetch(R, s + D);
+
+    wv = wv - lr * g;
+    // compiler-only ordering point between steps (one wave, no LDS)
+    __builtin_amdgcn_wave_barrier();
+  };
+
+#pragma unroll
+  for (int j = 0; j < D; ++j) prefetch(ring[j], j);
+  int s = 0;
+  for (; s + D <= S; s += D) {
+#pragma unroll
+    for (int j = 0; j < D; ++j) body(ring[j], s + j);
+  }
+#pragma unroll
+  for (int j = 0; j < D - 1; ++j)
+    if (s + j < S) body(ring[j], s + j);
+
+  if (lane < K_) param[w_off + lane] = wv;
+  if (lane == K_) param[b_off] = wv;
+  if (loss_out) {
+    float loss_last = 0.f;
+    if (use_mse) {
+      // the spec kernel's reduction over the last step's residuals: four
+      // partial sums on lanes 0/16/32/48, rows tm*16 + q*4 + i accumulated
+      // in (tm, i) order, zeros elsewhere, then the same butterfly
+      const int r = lane & 15, q = lane >> 4;
+      float loss_acc = 0.f;
+#pragma unroll
+      for (int tm = 0; tm < B_ / 16; ++tm)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const float dd = __shfl(d_last, tm * 16 + q * 4 + i, 64);
+          // explicit fma: the spec kernel's `loss_acc += d * d` compiles
+          // to one contracted v_fma per row; here the same source form
+          // gets SLP-vectorized into v_pk_mul + separate adds instead
+          if (r == 0) loss_acc = __builtin_fmaf(dd, dd, loss_acc);
+        }
+      loss_last = wave_sum(loss_acc);
+    }
+    if (lane == 0) *loss_out = use_mse ? loss_last / (float)B_ : 0.f;
+  }
+}
+
+// Process-wide implementation selector for the fp32 (32|64, 20) multi-step
+// fast path: the chain kernel by default, the MFMA spec kernel on request
+// (tests and A/B runs need both). Initialised once from
+// MI355X_TOY_MULTISTEP (chain | mfma).
+enum : int { kImplChain = 0, kImplMfma = 1 };
+static int impl_from_env() {
+  const char* e = std::getenv("MI355X_TOY_MULTISTEP");
+  if (e == nullptr || *e == '\0' || std::string(e) == "chain") return kImplChain;
+  TORCH_CHECK(std::string(e) == "mfma",
+              "MI355X_TOY_MULTISTEP must be 'chain' or 'mfma', got '", e, "'");
+  return kImplMfma;
+}
+static std::atomic<int>& multistep_impl() {
+  static std::atomic<int> impl{impl_from_env()};
+  return impl;
+}
+static std::atomic<int> g_chain_depth{0};  // 0 = measured default
+
+void set_toy_multistep_impl(const std::string& name) {
+  TORCH_CHECK(name == "chain" || name == "mfma",
+              "toy multistep impl must be 'chain' or 'mfma', got '", name, "'");
+  multistep_impl().store(name == "chain" ? kImplChain : kImplMfma);
+}
+std::string get_toy_multistep_impl() {
+  return multistep_impl().load() == kImplChain ? "chain" : "mfma";
+}
+void set_toy_multistep_chain_depth(int64_t depth) {
+  TORCH_CHECK(depth == 0 || (depth >= 2 && depth <= 4),
+              "chain prefetch depth must be 0 (default), 2, 3 or 4");
+  g_chain_depth.store((int)depth);
+}
+
+// measured at S = 1024 on fresh tiles: D = 2 / 3 / 4 -> 335 / 329 / 319 ns/step
+static constexpr int kChainDefaultDepth = 4;
+
+template <int B_>
+static void launch_toy_multistep_chain(const float* xp, const float* tp,
+                                       float* pp, float* lossp, bool use_mse,
+                                       int w_off, int b_off, float lr, int S) {
+  int depth = g_chain_depth.load();
+  if (depth == 0) depth = kChainDefaultDepth;
+  // rows are 80 B, so every row start is 16-byte aligned iff the base is
+  const bool vec4 = (reinterpret_cast<uintptr_t>(xp) & 15u) == 0;
+  auto go = [&](auto kptr) {
+    hipLaunchKernelGGL(kptr, dim3(1), dim3(64), 0, cur_stream(), xp, tp, pp,
+                       lossp, S, use_mse ? 1 : 0, w_off, b_off, lr);
+  };
+  auto by_depth = [&](auto vec) {
+    constexpr bool V = decltype(vec)::value;
+    if constexpr (B_ == 64) {
+      // 85 operand registers per set: a third set spills into AGPR copies
+      go(k_toy_multistep_chain<64, 20, 2, V>);
+    } else {
+      if (depth == 2) go(k_toy_multistep_chain<B_, 20, 2, V>);
+      else if (depth == 3) go(k_toy_multistep_chain<B_, 20, 3, V>);
+      else go(k_toy_multistep_chain<B_, 20, 4, V>);
+    }
+  };
+  if (vec4) by_depth(std::true_type{});
+  else by_depth(std::false_type{});
+}
+
 template <typename T>
 static void launch_toy_multistep(const torch::Tensor& x, const torch::Tensor& t,
                                  torch::Tensor& param_flat, float* lossp,
@@ -1680,6 +1916,18 @@ static void launch_toy_multistep(const torch::Tensor& x, const torch::Tensor& t,
   const T* xp = cdptr<T>(x);
   const T* tp = cdptr<T>(t);
   T* pp = dptr<T>(param_flat);
+  if constexpr (std::is_same<T, float>::value) {
+    if ((B == 32 || B == 64) && K == 20 &&
+        multistep_impl().load() == kImplChain) {
+      if (B == 32)
+        launch_toy_multistep_chain<32>(xp, tp, pp, lossp, use_mse, w_off,
+                                       b_off, lr, S);
+      else
+        launch_toy_multistep_chain<64>(xp, tp, pp, lossp, use_mse, w_off,
+                                       b_off, lr, S);
+      return;
+    }
+  }
   if (B == 32 && K == 20) {  // the reference shape: compile-time fast path
     if constexpr (std::is_same<T, __hip_bfloat16>::value) {
       // native bf16 MFMA (16x16x32): whole contraction in one MFMA/tile

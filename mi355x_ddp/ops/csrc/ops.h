@@ -3,6 +3,7 @@
 #pragma once
 #include <torch/extension.h>
 #include <cstdint>
+#include <string>
 
 #include "p2p_mesh.h"
 
@@ -88,6 +89,16 @@ std::vector<torch::Tensor> epoch_shard_multi(torch::Tensor X, torch::Tensor Tg,
 void toy_multistep(torch::Tensor x, torch::Tensor t, torch::Tensor param_flat,
                    torch::Tensor loss_out, bool use_mse,
                    int64_t w_off, int64_t b_off, double lr, int64_t batch);
+
+// Process-wide kernel selector for the fp32 batch-32/64, K-20 multi-step
+// fast path: "chain" (lane-parallel fmaf chains on the vector ALU, the
+// default) or "mfma" (k_toy_multistep_spec). Both produce the same bits.
+// Initialised from MI355X_TOY_MULTISTEP. The chain kernel's prefetch ring
+// depth (2, 3 or 4; 0 = the measured default) is a tuning aid for
+// tools/bench_multistep_curve.py.
+void set_toy_multistep_impl(const std::string& name);
+std::string get_toy_multistep_impl();
+void set_toy_multistep_chain_depth(int64_t depth);
 
 // Multi-step trainer with an IN-KERNEL xGMI mesh all-reduce per step
 // (world > 1): the deferred-launch engine at any world size, one

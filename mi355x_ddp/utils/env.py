@@ -20,6 +20,11 @@ MI355X_EPOCH_BLOCK      epochs gathered per epoch_shard_multi launch in
                         bench.py, letting the multistep launch span epoch
                         boundaries (default: fills the engine's max_defer
                         window; 1 = per-epoch gathers)
+MI355X_TOY_MULTISTEP    fp32 multi-step kernel at batch 32/64, K 20: chain
+                        (default; lane-parallel fmaf chains on the vector
+                        ALU) | mfma (k_toy_multistep_spec). Same bits
+                        either way; read once by the native extension,
+                        ext.set_toy_multistep_impl() switches at run time
 MI355X_ENGINE           fast-engine selection for the entrypoint scripts
                         (hooks default | hooks-graph | auto | fused |
                         persistent | graph; silently falls back to hooks
