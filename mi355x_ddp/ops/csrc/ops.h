@@ -1,5 +1,7 @@
 // Host-side launcher declarations for the MI355X (gfx950) kernel pack.
-// Implementations in kernels.hip; bound to Python in bindings.cpp.
+// Implementations in kernels.hip and, for the toy training-step family
+// (toy_fused_fwd_bwd, toy_multistep*), toy_kernels.hip; bound to Python in
+// bindings.hip.
 #pragma once
 #include <torch/extension.h>
 #include <cstdint>
@@ -83,9 +85,13 @@ std::vector<torch::Tensor> epoch_shard_multi(torch::Tensor X, torch::Tensor Tg,
 
 // Multi-step persistent toy trainer (world-1): x is [S*batch, K] of S
 // consecutive batches; runs S full fwd+loss+bwd+SGD steps in ONE launch
-// with the weights resident in LDS (bitwise-identical per-step arithmetic
-// to toy_fused_fwd_bwd with in-kernel SGD). loss_out, when non-empty,
-// receives the LAST step's loss.
+// (bitwise-identical per-step arithmetic to toy_fused_fwd_bwd with
+// in-kernel SGD for f32). Dispatch: batch 32/64 with K 20 takes a
+// compile-time kernel — fp32 the chain or MFMA spec kernel (selector below),
+// bf16 the wide-MFMA k_toy_multistep_bf16w, which matches to bf16 accuracy;
+// every other B <= 128, K <= 32 takes the generic k_toy_multistep, which
+// shares its tile step with the single-step kernel. loss_out, when
+// non-empty, receives the LAST step's loss.
 void toy_multistep(torch::Tensor x, torch::Tensor t, torch::Tensor param_flat,
                    torch::Tensor loss_out, bool use_mse,
                    int64_t w_off, int64_t b_off, double lr, int64_t batch);

@@ -53,7 +53,7 @@ class P2pMesh {
   int world() const { return world_; }
 
   // device-view accessors for kernels that embed the mesh exchange
-  // (toy_multistep_mesh in kernels.hip)
+  // (toy_multistep_mesh in toy_kernels.hip)
   MeshSlot* my_mb() const { return my_mb_; }
   MeshSlot* const* peer_slots() const { return peer_slot_dev_; }
   unsigned int* err_flag() const { return err_host_; }

@@ -1,23 +1,13 @@
 // See p2p_mesh.h. Native HIP for gfx950; no CUDA compatibility paths.
 #include "p2p_mesh.h"
 
-#include <ATen/hip/HIPContext.h>
-#include <c10/hip/HIPStream.h>
-#include <hip/hip_bf16.h>
+#include <hip/hip_runtime.h>
 
 #include <cstring>
 
-#define HIP_OK(expr)                                                          \
-  do {                                                                        \
-    hipError_t _e = (expr);                                                   \
-    TORCH_CHECK(_e == hipSuccess, "HIP error: ", hipGetErrorString(_e));      \
-  } while (0)
+#include "kernel_common.h"
 
 namespace mi355x {
-
-static hipStream_t cur_stream() {
-  return c10::hip::getCurrentHIPStream().stream();
-}
 
 // ~5 s at the 100 MHz constant s_memrealtime clock: generous enough that
 // rank skew (first-launch overheads, allocator warmup) can never trip a
@@ -26,32 +16,13 @@ static hipStream_t cur_stream() {
 static constexpr unsigned long long kTimeout = 500ull * 1000 * 1000;
 
 template <typename T>
-__device__ __forceinline__ float mesh_ldf(const T* p);
-template <>
-__device__ __forceinline__ float mesh_ldf<float>(const float* p) { return *p; }
-template <>
-__device__ __forceinline__ float mesh_ldf<__hip_bfloat16>(
-    const __hip_bfloat16* p) {
-  return __bfloat162float(*p);
-}
-template <typename T>
-__device__ __forceinline__ void mesh_stf(T* p, float v);
-template <>
-__device__ __forceinline__ void mesh_stf<float>(float* p, float v) { *p = v; }
-template <>
-__device__ __forceinline__ void mesh_stf<__hip_bfloat16>(__hip_bfloat16* p,
-                                                         float v) {
-  *p = __float2bfloat16(v);
-}
-
-template <typename T>
 __global__ void __launch_bounds__(64, 1)
 k_mesh_allreduce(T* __restrict__ grad, int n, unsigned long long seq,
                  MeshSlot* const* __restrict__ peer_slots,
                  MeshSlot* __restrict__ my_mb, int world, int inv_scale_world,
                  unsigned int* __restrict__ err_host) {
   const int t = threadIdx.x;
-  const float g = (t < n) ? mesh_ldf(&grad[t]) : 0.f;
+  const float g = (t < n) ? ldf(&grad[t]) : 0.f;
 
   // scatter my contribution into slot[rank] of every rank's mailbox
   for (int p = 0; p < world; ++p) {
@@ -86,7 +57,7 @@ k_mesh_allreduce(T* __restrict__ grad, int n, unsigned long long seq,
   if (t < n) {
     float sum = 0.f;
     for (int p = 0; p < world; ++p) sum += my_mb[p].data[t];
-    mesh_stf(&grad[t], sum * __int_as_float(inv_scale_world));
+    stf(&grad[t], sum * __int_as_float(inv_scale_world));
   }
 }
 

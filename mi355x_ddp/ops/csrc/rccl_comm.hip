@@ -3,14 +3,7 @@
 #include <cstdlib>
 #include "rccl_comm.h"
 
-#include <ATen/hip/HIPContext.h>
-#include <c10/hip/HIPStream.h>
-
-#define HIP_OK(expr)                                                          \
-  do {                                                                        \
-    hipError_t _e = (expr);                                                   \
-    TORCH_CHECK(_e == hipSuccess, "HIP error: ", hipGetErrorString(_e));      \
-  } while (0)
+#include "kernel_common.h"
 
 #define NCCL_OK(expr)                                                         \
   do {                                                                        \
@@ -30,10 +23,6 @@ static ncclDataType_t nccl_dtype(const torch::Tensor& t) {
     case at::kLong: return ncclInt64;
     default: TORCH_CHECK(false, "unsupported dtype for RCCL: ", t.scalar_type());
   }
-}
-
-static hipStream_t cur_stream() {
-  return c10::hip::getCurrentHIPStream().stream();
 }
 
 std::string RcclComm::make_unique_id() {

@@ -17,6 +17,7 @@ ext = CUDAExtension(
     name="mi355x_ddp._C",
     sources=[
         "mi355x_ddp/ops/csrc/kernels.hip",
+        "mi355x_ddp/ops/csrc/toy_kernels.hip",
         "mi355x_ddp/ops/csrc/rccl_comm.hip",
         "mi355x_ddp/ops/csrc/p2p_mesh.hip",
         "mi355x_ddp/ops/csrc/reducer_core.hip",

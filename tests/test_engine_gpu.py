@@ -237,15 +237,25 @@ def test_trainer_fast_engine_matches_hooks_on_gpu(tmp_path):
         (w_fast - w_hooks).abs().max()
 
 
-def test_generic_multistep_odd_shape_bitwise():
-    # shapes off the (32,20) fast path take the generic rolled kernel —
-    # hold it to the same bitwise-vs-single-step contract (B=48, K=12)
+# shapes off the (32|64, 20) fast paths, one per path of the generic tile
+# step: (48, 12) free db column; (16, 16) K a multiple of 16, the wave-sum db
+# fallback; (33, 32) two K-tiles with the fallback and a ragged last M-tile;
+# (17, 17) db column in the second K-tile; (5, 3) one partial tile;
+# (128, 20) the largest instantiation <8,2>, 3 steps
+@pytest.mark.parametrize("B,K,dtype", [
+    (48, 12, torch.float32), (16, 16, torch.float32), (33, 32, torch.float32),
+    (17, 17, torch.float32), (5, 3, torch.float32), (128, 20, torch.float32),
+    (48, 12, torch.bfloat16), (16, 16, torch.bfloat16)],
+    ids=lambda v: str(v).replace("torch.", ""))
+def test_generic_multistep_odd_shape_bitwise(B, K, dtype):
+    # the generic rolled kernel is held to the same bitwise-vs-single-step
+    # contract as the fast paths
     from mi355x_ddp import ops
     from mi355x_ddp.models import toy_model
 
     def params(seed=7):
         torch.manual_seed(seed)
-        m = toy_model(12, 1).to(DEV)
+        m = toy_model(K, 1).to(DEV).to(dtype)
         from mi355x_ddp.parallel.reducer import Reducer
         red = Reducer(list(m.parameters()), comm=None)
         b = red.buckets[0]
@@ -253,21 +263,23 @@ def test_generic_multistep_odd_shape_bitwise():
         _, bidx = red._param_index[m.bias]
         return m, b.flat_param, b.flat_grad, b.offsets[widx], b.offsets[bidx]
 
+    S = 3 if B == 128 else 6
     g = torch.Generator().manual_seed(4)
-    X = torch.rand(6 * 48, 12, generator=g).to(DEV)
-    T = torch.rand(6 * 48, 1, generator=g).to(DEV)
+    X = torch.rand(S * B, K, generator=g).to(DEV).to(dtype)
+    T = torch.rand(S * B, 1, generator=g).to(DEV).to(dtype)
 
     m1, p1, g1, w1, b1 = params()
-    for s in range(6):
-        ops.ext().toy_fused_fwd_bwd(X[s * 48:(s + 1) * 48].contiguous(),
-                                    T[s * 48:(s + 1) * 48].contiguous(),
+    for s in range(S):
+        ops.ext().toy_fused_fwd_bwd(X[s * B:(s + 1) * B].contiguous(),
+                                    T[s * B:(s + 1) * B].contiguous(),
                                     p1, g1, torch.Tensor(), True, w1, b1, 0.05)
     torch.cuda.synchronize()
 
     m2, p2, g2, w2, b2 = params()
-    ops.ext().toy_multistep(X, T, p2, torch.Tensor(), True, w2, b2, 0.05, 48)
+    assert not torch.equal(p1, p2)  # the steps moved the params
+    ops.ext().toy_multistep(X, T, p2, torch.Tensor(), True, w2, b2, 0.05, B)
     torch.cuda.synchronize()
-    assert torch.equal(p1, p2), (p1 - p2).abs().max()
+    assert torch.equal(p1, p2), (p1.float() - p2.float()).abs().max()
 
 
 def test_persistent_deferral_state_machine_fuzz():

@@ -143,16 +143,30 @@ def test_flatten_unflatten_roundtrip():
         assert t.abs().sum() == 0
 
 
-def test_toy_fused_step_matches_reference():
-    B, K = 32, 20
+# (32, 20) is the flagship shape; the rest walk the generic tile step's
+# paths: (16, 16) K a multiple of 16 (wave-sum db fallback), (33, 32) two
+# K-tiles with the fallback and a ragged last M-tile, (17, 17) the db column
+# in the second K-tile, (5, 3) one partial tile, (128, 20) the largest
+# instantiation <8,2>.
+TOY_SHAPES = [(32, 20), (48, 12), (16, 16), (33, 32), (17, 17), (5, 3),
+              (128, 20)]
+
+
+def _toy_buffers(K, w, b):
+    n = (K + 1 + 3) & ~3  # [w(K) | b | pad] padded to 4
+    param = torch.zeros(n, device=DEV)
+    param[:K] = w.flatten()
+    param[K] = b[0]
+    return param, torch.zeros(n, device=DEV)
+
+
+@pytest.mark.parametrize("B,K", TOY_SHAPES)
+def test_toy_fused_step_matches_reference(B, K):
     x = _rand(B, K, seed=30).to(DEV)
     t = _rand(B, 1, seed=31).to(DEV)
     w = (_rand(1, K, seed=32) - 0.5).to(DEV)
     b = _rand(1, seed=33).to(DEV)
-    param = torch.zeros(24, device=DEV)  # [w(20) | b | pad] padded to 4
-    param[:K] = w.flatten()
-    param[K] = b[0]
-    grad = torch.zeros(24, device=DEV)
+    param, grad = _toy_buffers(K, w, b)
     loss_out = torch.zeros((), device=DEV)
     ops.ext().toy_fused_fwd_bwd(x, t, param, grad, loss_out, True, 0, K, 0.0)
 
@@ -166,17 +180,15 @@ def test_toy_fused_step_matches_reference():
     assert torch.allclose(grad[K].cpu(), bc.grad[0], atol=1e-5)
 
 
-def test_toy_fused_inkernel_sgd():
+@pytest.mark.parametrize("B,K", TOY_SHAPES)
+def test_toy_fused_inkernel_sgd(B, K):
     # lr > 0 path: one launch does fwd+bwd+SGD; matches torch step exactly
-    B, K, LR = 32, 20, 0.1
+    LR = 0.1
     x = _rand(B, K, seed=40).to(DEV)
     t = _rand(B, 1, seed=41).to(DEV)
     w = (_rand(1, K, seed=42) - 0.5).to(DEV)
     b = _rand(1, seed=43).to(DEV)
-    param = torch.zeros(24, device=DEV)
-    param[:K] = w.flatten()
-    param[K] = b[0]
-    grad = torch.zeros(24, device=DEV)
+    param, grad = _toy_buffers(K, w, b)
     ops.ext().toy_fused_fwd_bwd(x, t, param, grad, torch.Tensor(), True,
                                 0, K, LR)
     wc = w.cpu().requires_grad_(True)
