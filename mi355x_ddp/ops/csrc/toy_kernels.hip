@@ -9,9 +9,10 @@
 // fp32 world-1 multi-step fast path (batch 32/64, K 20):
 // `k_toy_multistep_chain` runs the same k-ordered fmaf chains the f32 MFMA
 // evaluates, bit for bit, on the vector ALU — one row (forward) / one
-// column (backward) per lane, cross-lane hand-offs by v_readlane broadcast,
-// no LDS and no barrier — because those MFMA tiles discard 15/16 of their
-// work on the serial critical path (3.6x faster in kernel, profiles r03a).
+// column (backward) per lane, cross-lane hand-offs folded into the
+// multiply-add as DPP row broadcasts (v_fmac_f32_dpp row_newbcast), no LDS
+// and no barrier — because those MFMA tiles discard 15/16 of their work on
+// the serial critical path (4.1x faster in kernel, profiles r03a, r03c).
 // The MFMA spec kernel stays selectable (set_toy_multistep_impl /
 // MI355X_TOY_MULTISTEP).
 //
@@ -793,17 +794,96 @@ k_toy_multistep_spec(const T* __restrict__ X, const T* __restrict__ Tg,
 // B_ = 8x4 (or 16x4) and K_ = 5x4 fill the MFMA k-groups exactly, so the
 // MFMA chain order is the plain index order with no padding terms. The two
 // cross-lane hand-offs are broadcasts of wave-uniform values (w[k] to the
-// row lanes, dy[i] to the column lanes): v_readlane_b32 with a constant
-// lane puts each in an SGPR the v_fma reads directly — no LDS, no barrier.
+// row lanes, dy[i] to the column lanes), and they cost no instruction per
+// term: the multiply-add itself reads the broadcast lane, as
+// `v_fmac_f32_dpp acc, src, x row_newbcast:n` (first factor = lane n of
+// the reading lane's own 16-lane row). Chain k lives in lane k — row 0
+// holds k = 0..15, row 1 holds k = 16..19 and the bias/db lane 20 — so one
+// v_permlane16_swap per hand-off (bcast_rows01) first copies the value's
+// rows 0 and 1 into every row that reads them; at batch 64 a
+// v_permlane32_swap in front also carries rows 2 and 3 down. The DPP reads
+// need EXEC full, which holds through the whole step loop (no divergent
+// branch; lanes 21..63 compute unused copies). No LDS, no barrier.
 // Operands stream through a ring of D register sets (distance-D prefetch,
 // unrolled by D like the bf16 kernel's setA/setB): rows as 16-byte loads
 // when VEC4 (tile base 16-byte aligned; rows are 80 B), columns as dwords.
 // Loads are unconditional with clamped addresses and never pass tile S-1.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ float lane_bcast(float v, int src_lane) {
-  return __int_as_float(
-      __builtin_amdgcn_readlane(__float_as_int(v), src_lane));
+
+// Rows 0 and 1 (lanes 0..15, 16..31) of a per-lane value, each copied into
+// BOTH rows of its half-wave: lo = {r0, r0, r2, r2}, hi = {r1, r1, r3, r3}.
+// The builtin, not asm, so the compiler pads the swap's own hazards.
+struct RowPair {
+  float lo, hi;
+};
+__device__ __forceinline__ RowPair bcast_rows01(float v) {
+  const unsigned u = __float_as_uint(v);
+  const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+  return {__uint_as_float(r[0]), __uint_as_float(r[1])};
 }
+// Both half-waves of a per-lane value copied into both: lo = {r0, r1, r0,
+// r1}, hi = {r2, r3, r2, r3}.
+__device__ __forceinline__ RowPair bcast_halves(float v) {
+  const unsigned u = __float_as_uint(v);
+  const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+  return {__uint_as_float(r[0]), __uint_as_float(r[1])};
+}
+
+// acc = fmaf(src[lane n of the reader's row], x, acc): the same fused
+// operation, operand order and rounding as the v_fmac_f32 the compiler
+// selects for __builtin_fmaf; only where the first factor is read differs.
+// The compiler does not fold a DPP broadcast into the fma by itself
+// (update_dpp becomes v_mov_b32_dpp + v_fmac), hence asm; and one asm
+// statement per term gets an s_nop between every two, hence whole runs of
+// terms per statement (clang allows 30 operands). "+v" on the accumulator
+// keeps the statements in chain order.
+#define BC_DPP(n) " row_newbcast:" #n " row_mask:0xf bank_mask:0xf\n\t"
+#define BC_FMAC(src, x, n) \
+  "v_fmac_f32_dpp %[acc], %[" #src "], %[" #x "]" BC_DPP(n)
+#define BC_FMAC4(src, p, n0, n1, n2, n3)                  \
+  BC_FMAC(src, p##0, n0) BC_FMAC(src, p##1, n1)           \
+  BC_FMAC(src, p##2, n2) BC_FMAC(src, p##3, n3)
+#define BC_FMAC16(src, p)                                             \
+  BC_FMAC4(src, p##0, 0, 1, 2, 3) BC_FMAC4(src, p##1, 4, 5, 6, 7)     \
+  BC_FMAC4(src, p##2, 8, 9, 10, 11) BC_FMAC4(src, p##3, 12, 13, 14, 15)
+#define BC_IN4(p, x)                                            \
+  [p##0] "v"((x)[0]), [p##1] "v"((x)[1]), [p##2] "v"((x)[2]),   \
+  [p##3] "v"((x)[3])
+#define BC_IN16(p, x)                                     \
+  BC_IN4(p##0, (x)) , BC_IN4(p##1, (x) + 4),              \
+  BC_IN4(p##2, (x) + 8), BC_IN4(p##3, (x) + 12)
+// gfx9 wants 2 wait states between a VALU write of a VGPR and a DPP read
+// of it, and the hazard recogniser does not look inside asm: a statement
+// that may directly follow the swap that wrote its DPP source pads itself.
+#define BC_PAD "s_nop 1\n\t"
+
+// forward: y = sum_k w[k] * x[k] from +0 in k order (w[0..15] in row 0 =
+// w.lo, w[16..19] in row 1 = w.hi), then + bias (lane 20 = lane 4 of row 1)
+__device__ __forceinline__ float chain_fwd20(const RowPair& w,
+                                             const float (&x)[20]) {
+  float acc = 0.f;
+  asm(BC_PAD BC_FMAC16(lo, a) BC_FMAC4(hi, b, 0, 1, 2, 3)
+      "v_add_f32_dpp %[acc], %[hi], %[acc]" BC_DPP(4)
+      : [acc] "+v"(acc)
+      : [lo] "v"(w.lo), [hi] "v"(w.hi), BC_IN16(a, x), BC_IN4(b, x + 16));
+  return acc;
+}
+// backward: 16 terms acc += src[n] * x[n], n = 0..15 in order
+template <bool PAD>
+__device__ __forceinline__ void chain_bwd16(float& acc, float src,
+                                            const float* x) {
+  if constexpr (PAD)
+    asm(BC_PAD BC_FMAC16(s, a) : [acc] "+v"(acc) : [s] "v"(src), BC_IN16(a, x));
+  else
+    asm(BC_FMAC16(s, a) : [acc] "+v"(acc) : [s] "v"(src), BC_IN16(a, x));
+}
+#undef BC_PAD
+#undef BC_IN16
+#undef BC_IN4
+#undef BC_FMAC16
+#undef BC_FMAC4
+#undef BC_FMAC
+#undef BC_DPP
 
 // A tile of ones with the X tile's row pitch: the db lane (and the idle
 // lanes above it) stream their backward operand from here with the same
@@ -872,27 +952,33 @@ k_toy_multistep_chain(const float* __restrict__ X,
 
   float d_last = 0.f;
   auto body = [&](CSet& R, int s) {
-    // ---- forward: y = X @ w, k-ordered chain from +0 ----
-    float wk[K_ + 1];
-#pragma unroll
-    for (int k = 0; k <= K_; ++k) wk[k] = lane_bcast(wv, k);
-    float y = 0.f;
-#pragma unroll
-    for (int k = 0; k < K_; ++k) y = __builtin_fmaf(R.xr[k], wk[k], y);
-    const float bterm = wk[K_];
+    // ---- forward: y = X @ w + b, k-ordered chain from +0 ----
+    // rows 0/1 of wv reach every row that owns a batch row: rows 0..1 at
+    // B_ = 32 (rows 2..3 run on copies of the bias, unused), all at 64
+    const RowPair w = bcast_rows01(B_ == 64 ? bcast_halves(wv).lo : wv);
+    const float y = chain_fwd20(w, R.xr);
 
     // ---- loss grad: one row per lane ----
-    const float d = y + bterm - R.t;
+    const float d = y - R.t;
     const float dy = use_mse ? d * inv2B : 0.f;
     d_last = d;
 
     // ---- backward: dw_k = sum_i dY_i X[i,k]; db on the ones lane ----
-    float dyi[B_];
-#pragma unroll
-    for (int i = 0; i < B_; ++i) dyi[i] = lane_bcast(dy, i);
+    // dy[i] lives in lane i; the chains live in rows 0..1. Only the first
+    // reader of each swap's pair pads: the second runs 16 terms later.
     float g = 0.f;
-#pragma unroll
-    for (int i = 0; i < B_; ++i) g = __builtin_fmaf(dyi[i], R.xc[i], g);
+    if constexpr (B_ == 64) {
+      const RowPair h = bcast_halves(dy);
+      const RowPair p01 = bcast_rows01(h.lo), p23 = bcast_rows01(h.hi);
+      chain_bwd16<true>(g, p01.lo, R.xc);
+      chain_bwd16<false>(g, p01.hi, R.xc + 16);
+      chain_bwd16<true>(g, p23.lo, R.xc + 32);
+      chain_bwd16<false>(g, p23.hi, R.xc + 48);
+    } else {
+      const RowPair p = bcast_rows01(dy);
+      chain_bwd16<true>(g, p.lo, R.xc);
+      chain_bwd16<false>(g, p.hi, R.xc + 16);
+    }
 
     // this set's regs are dead from here: refill them for step s + D
     prefetch(R, s + D);
@@ -971,8 +1057,11 @@ void set_toy_multistep_chain_depth(int64_t depth) {
   g_chain_depth.store((int)depth);
 }
 
-// measured at S = 1024 on fresh tiles: D = 2 / 3 / 4 -> 335 / 329 / 319 ns/step
-static constexpr int kChainDefaultDepth = 4;
+// Measured on fresh tiles at batch 32 (profiles r03c), D = 2 / 3 / 4:
+// S = 1024 -> 281 / 282 / 281 ns/step, S = 64 -> 304 / 306 / 307. Depth no
+// longer pays (with the readlane broadcasts it was 335 / 329 / 319), so the
+// default is the smallest ring: 129 VGPRs instead of 254.
+static constexpr int kChainDefaultDepth = 2;
 
 template <int B_>
 static void launch_toy_multistep_chain(const float* xp, const float* tp,
@@ -989,7 +1078,8 @@ static void launch_toy_multistep_chain(const float* xp, const float* tp,
   auto by_depth = [&](auto vec) {
     constexpr bool V = decltype(vec)::value;
     if constexpr (B_ == 64) {
-      // 85 operand registers per set: a third set spills into AGPR copies
+      // 85 operand registers per set: a third set still needs AGPR copies
+      // (293 registers), and depth stopped paying at batch 32 anyway
       go(k_toy_multistep_chain<64, 20, 2, V>);
     } else {
       if (depth == 2) go(k_toy_multistep_chain<B_, 20, 2, V>);
