@@ -10,9 +10,11 @@
 // `k_toy_multistep_chain` runs the same k-ordered fmaf chains the f32 MFMA
 // evaluates, bit for bit, on the vector ALU — one row (forward) / one
 // column (backward) per lane, cross-lane hand-offs folded into the
-// multiply-add as DPP row broadcasts (v_fmac_f32_dpp row_newbcast), no LDS
-// and no barrier — because those MFMA tiles discard 15/16 of their work on
-// the serial critical path (4.1x faster in kernel, profiles r03a, r03c).
+// multiply-add as DPP row broadcasts (v_fmac_f32_dpp row_newbcast) —
+// because those MFMA tiles discard 15/16 of their work on the serial
+// critical path (profiles r03a, r03c). One wave computes; loader waves on
+// the other SIMDs feed it through an LDS ring, one workgroup barrier per
+// chunk of steps (profiles r03d).
 // The MFMA spec kernel stays selectable (set_toy_multistep_impl /
 // MI355X_TOY_MULTISTEP).
 //
@@ -803,11 +805,13 @@ k_toy_multistep_spec(const T* __restrict__ X, const T* __restrict__ Tg,
 // rows 0 and 1 into every row that reads them; at batch 64 a
 // v_permlane32_swap in front also carries rows 2 and 3 down. The DPP reads
 // need EXEC full, which holds through the whole step loop (no divergent
-// branch; lanes 21..63 compute unused copies). No LDS, no barrier.
-// Operands stream through a ring of D register sets (distance-D prefetch,
-// unrolled by D like the bf16 kernel's setA/setB): rows as 16-byte loads
-// when VEC4 (tile base 16-byte aligned; rows are 80 B), columns as dwords.
-// Loads are unconditional with clamped addresses and never pass tile S-1.
+// branch; lanes 21..63 compute unused copies).
+// That wave is bound by its own instruction issue, so it issues nothing
+// but the chain and 14 (22 at batch 64) LDS reads per step: loader waves on
+// the CU's other SIMDs fetch the tiles and stage them in an LDS ring, once
+// row-major and once transposed (ChainSlot and the kernel's comment below).
+// The compute wave keeps two operand register sets and fetches step s + 1
+// from LDS while step s computes.
 // ---------------------------------------------------------------------------
 
 // Rows 0 and 1 (lanes 0..15, 16..31) of a per-lane value, each copied into
@@ -885,73 +889,206 @@ __device__ __forceinline__ void chain_bwd16(float& acc, float src,
 #undef BC_FMAC
 #undef BC_DPP
 
-// A tile of ones with the X tile's row pitch: the db lane (and the idle
-// lanes above it) stream their backward operand from here with the same
-// immediate offsets as a real column, so the constant-1 column costs no
-// per-term select on the chain. Deliberately not `const`: a const device
-// variable lands in the constant address space, and a pointer select
-// between it and the global X pointer degrades every column load to a FLAT
-// load, whose out-of-order return forces full vmcnt(0) drains.
-template <int N>
-struct OnesTile {
-  float v[N];
-  constexpr OnesTile() : v() {
-    for (int i = 0; i < N; ++i) v[i] = 1.f;
-  }
+// LDS slot of one training step, filled by the loader waves: the X tile
+// twice (row-major for the forward, transposed for the backward) plus its
+// targets. All in dwords.
+//   row image   [B][K]        lane m reads row m as K/4 ds_read_b128; the
+//                             80-byte pitch puts any 16 rows with distinct
+//                             m mod 16 on 16 disjoint 4-bank groups
+//   transposed  [K + 1][B + 4] lane k reads row k (= column k of X) as B/4
+//                             ds_read_b128; the pitch (36 / 68 dwords)
+//                             likewise spreads 16 rows with distinct
+//                             k mod 16 over all 64 banks. Row K is the
+//                             constant-ones column of db: written once per
+//                             slot, never rewritten. Columns B..B+3 are
+//                             padding, never read.
+//   targets     [B]
+// A ds_read_b128 is served in four groups of 16 lanes whose lane numbers
+// are distinct mod 16, so both images read conflict-free as long as lane l
+// reads row l or row l mod 16.
+template <int B_, int K_>
+struct ChainSlot {
+  static constexpr int kPitch = B_ + 4;
+  static constexpr int kRow = 0;
+  static constexpr int kTr = B_ * K_;
+  static constexpr int kOnes = kTr + K_ * kPitch;
+  static constexpr int kTgt = kTr + (K_ + 1) * kPitch;
+  static constexpr int kSize = kTgt + B_;  // 1428 (5712 B) / 2772 (11088 B)
+  // two ring halves of H slots in 64 KB of static LDS: H <= 5 / H <= 2
+  static constexpr int kMaxH = (64 * 1024 / 4) / kSize / 2;
+  static_assert(kSize % 4 == 0 && kTr % 4 == 0 && kPitch % 4 == 0 &&
+                    K_ % 4 == 0 && B_ % 4 == 0,
+                "every ds_read_b128 must be 16-byte aligned");
 };
-__device__ OnesTile<64 * 20> k_ones_tile{};
 
-template <int B_, int K_, int D, bool VEC4>
-__global__ void __launch_bounds__(64, 1)
+// Tiles the loaders keep in registers ahead of the one they are writing to
+// LDS. Their global loads stay in flight across the barriers, so the HBM
+// latency (~900 cycles) hides behind kChainTilesAhead tiles of loader work.
+static constexpr int kChainTilesAhead = 4;
+
+// One workgroup: wave 0 computes, waves 1..NL load. The loaders stage each
+// [B][K] tile (coalesced dword loads on the flat index, so no alignment
+// requirement on the base) into an LDS ring of two halves of H slots; the
+// compute wave works through half c & 1 (chunk c = steps cH .. cH + H - 1)
+// while the loaders fill the other half with chunk c + 1.
+//
+// Barrier protocol. Barrier c (c = 0 .. NC - 1, NC = ceil(S / H)) is the
+// only synchronisation, and every wave executes exactly NC of them, a
+// function of S and H alone; no wave returns before its last one.
+//   loaders   write chunk c, then arrive at barrier c
+//   compute   arrives at barrier c just before its first LDS read of
+//             chunk c, i.e. while step cH - 1 is still to be computed but
+//             already sits in registers (the barrier's lgkmcnt(0))
+// So passing barrier c tells the compute wave that chunk c is complete,
+// and tells the loaders that every read of chunk c - 1 has returned: its
+// half is free for chunk c + 1.
+// Invariant: the loaders never address a tile index >= S, in global memory
+// or in LDS. LDS writes are guarded on the step index; the slots the tail
+// of the last chunk skips keep stale data that the compute wave, which
+// reads steps < S only, never consumes. The run-ahead loads past the end
+// re-read tile S - 1 into registers that are never written out.
+template <int B_, int K_, int NL>
+__global__ void __launch_bounds__(64 * (1 + NL))
 k_toy_multistep_chain(const float* __restrict__ X,
                       const float* __restrict__ Tg,
                       float* __restrict__ param, float* __restrict__ loss_out,
-                      int S, int use_mse, int w_off, int b_off, float lr) {
-  static_assert((B_ == 32 || B_ == 64) && K_ == 20 && D >= 1,
-                "chain path: B in {32, 64}, K = 20 (k_ones_tile pitch)");
+                      int S, int H, int use_mse, int w_off, int b_off,
+                      float lr) {
+  static_assert((B_ == 32 || B_ == 64) && K_ == 20 && NL >= 1 && NL <= 3,
+                "chain path: B in {32, 64}, K = 20, one wave per SIMD");
+  using L = ChainSlot<B_, K_>;
+  __shared__ __attribute__((aligned(16))) float ring[2 * L::kMaxH * L::kSize];
+  // scalar wave index: the role branch is uniform, EXEC stays full
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+
+  if (wave != 0) {
+    // ---------------- loader waves ----------------
+    constexpr int NT = 64 * NL;                     // loader threads
+    constexpr int NX = (B_ * K_ + NT - 1) / NT;     // X dwords per lane/tile
+    constexpr bool kTail = (B_ * K_) % NT != 0;     // last dword partial
+    constexpr int R = kChainTilesAhead;
+    const int lt = (int)threadIdx.x - 64;
+    const int total = (S + H - 1) / H * H;  // NC whole chunks
+    float xv[R][NX], tv[R];
+
+    // Loads are unconditional, so that the compiler can count them and
+    // wait for exactly the oldest tile (a load inside a branch makes every
+    // wait behind it a full drain). Past the end the tile index is clamped
+    // to S - 1: those registers are never written to LDS.
+    auto load_tile = [&](float (&x)[NX], float& t, int tile) {
+      const int tc = tile < S ? tile : S - 1;
+      const float* xt = X + (size_t)tc * (B_ * K_);
+#pragma unroll
+      for (int i = 0; i < NX; ++i) {
+        const int f = lt + i * NT;
+        x[i] = xt[(kTail && i == NX - 1 && f >= B_ * K_) ? B_ * K_ - 1 : f];
+      }
+      t = Tg[(size_t)tc * B_ + (lt & (B_ - 1))];
+    };
+    auto write_tile = [&](const float (&x)[NX], float t, int slot) {
+      float* sl = ring + slot * L::kSize;
+#pragma unroll
+      for (int i = 0; i < NX; ++i) {
+        const int f = lt + i * NT;
+        if (!kTail || i < NX - 1 || f < B_ * K_) {
+          sl[L::kRow + f] = x[i];
+          sl[L::kTr + (f % K_) * L::kPitch + f / K_] = x[i];
+        }
+      }
+      if (lt < B_) sl[L::kTgt + lt] = t;
+    };
+
+#pragma unroll
+    for (int r = 0; r < R; ++r) load_tile(xv[r], tv[r], r);
+    if (lt < B_)
+      for (int sl = 0; sl < 2 * H; ++sl) ring[sl * L::kSize + L::kOnes + lt] = 1.f;
+    int slot = 0, togo = H;
+    for (int t0 = 0; t0 < total; t0 += R) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const int tile = t0 + r;
+        if (tile < S) write_tile(xv[r], tv[r], slot);
+        load_tile(xv[r], tv[r], tile + R);  // in flight across barriers
+        slot = (slot + 1 == 2 * H) ? 0 : slot + 1;
+        if (--togo == 0) {
+          togo = H;
+          if (tile < total) __syncthreads();  // barrier tile / H
+        }
+      }
+    }
+    return;
+  }
+
+  // ---------------- compute wave ----------------
   const int lane = threadIdx.x;
   const int mr = lane & (B_ - 1);  // row owned in the forward
+  // transposed-image row read in the backward: column `lane` of X for
+  // lanes < K_, the ones row for the db lane K_; the idle lanes above read
+  // row lane mod 16 to stay off the live lanes' banks
+  const int cr = (lane <= K_) ? lane : (lane & 15);
   const float inv2B = 2.f / (float)B_;
   // w[k] in lane k, bias in lane K_ (lanes above hold an unused copy)
   float wv = param[(lane < K_) ? w_off + lane : b_off];
-  // backward operand stream: column `lane` of X for lanes < K_, advancing
-  // one tile per step; the ones tile (never advancing) for lane K_ and up
-  const float* colp = (lane < K_) ? X + lane : k_ones_tile.v;
-  const size_t cstep = (lane < K_) ? (size_t)(B_ * K_) : 0;
+  const float* rowp = ring + L::kRow + mr * K_;
+  const float* colp = ring + L::kTr + cr * L::kPitch;
+  const float* tgtp = ring + L::kTgt + mr;
+
+  // One step's operands as they come out of LDS, 16 bytes per read
+  struct LSet {
+    f32x4 xr[K_ / 4];  // fwd: X[mr][0..K_)
+    f32x4 xc[B_ / 4];  // bwd: X[0..B_)[lane] (ones on the db lane)
+    float t;           // target of row mr
+  };
+  LSet setA, setB;
+
+  auto fetch = [&](LSet& R, int slot) {
+    const int o = slot * L::kSize;
+#pragma unroll
+    for (int j = 0; j < K_ / 4; ++j)
+      R.xr[j] = *reinterpret_cast<const f32x4*>(rowp + o + 4 * j);
+#pragma unroll
+    for (int j = 0; j < B_ / 4; ++j)
+      R.xc[j] = *reinterpret_cast<const f32x4*>(colp + o + 4 * j);
+    R.t = tgtp[o];
+  };
+  // Pass a set's registers through empty asm statements before its step
+  // starts and before the next set's reads are issued. Two things hang on
+  // it. The compiler can no longer see the chains take the reads apart
+  // dword by dword, so they stay ds_read_b128 (it otherwise splits some
+  // into ds_read2_b32 pairs with an address add each). And the one
+  // s_waitcnt of the step lands here, where everything outstanding was
+  // issued a whole step ago, instead of behind the freshly issued reads.
+  // (As few statements as clang's 30 asm operands allow: each one gets a
+  // wait of its own.)
+  auto settle = [&](LSet& R) {
+    static_assert(K_ == 20, "five row reads");
+    if constexpr (B_ == 64)
+      asm volatile(""
+                   : "+v"(R.xc[8]), "+v"(R.xc[9]), "+v"(R.xc[10]),
+                     "+v"(R.xc[11]), "+v"(R.xc[12]), "+v"(R.xc[13]),
+                     "+v"(R.xc[14]), "+v"(R.xc[15]));
+    asm volatile(""
+                 : "+v"(R.xr[0]), "+v"(R.xr[1]), "+v"(R.xr[2]), "+v"(R.xr[3]),
+                   "+v"(R.xr[4]), "+v"(R.xc[0]), "+v"(R.xc[1]), "+v"(R.xc[2]),
+                   "+v"(R.xc[3]), "+v"(R.xc[4]), "+v"(R.xc[5]), "+v"(R.xc[6]),
+                   "+v"(R.xc[7]), "+v"(R.t)
+                 :
+                 : "memory");
+  };
 
   struct CSet {
-    float xr[K_];  // fwd: X[mr][0..K_)
-    float xc[B_];  // bwd: X[0..B_)[lane] (ones on the db lane)
-    float t;       // target of row mr
+    float xr[K_];
+    float xc[B_];
+    float t;
   };
-  CSet ring[D];
-
-  // Unconditional loads; the step index is clamped to the last tile, so
-  // the D prefetches past the end re-read tile S-1 and nothing beyond it.
-  auto prefetch = [&](CSet& R, int s_raw) {
-    const int s = (s_raw < S) ? s_raw : S - 1;
-    const float* rowp = X + (size_t)s * (B_ * K_) + mr * K_;
-    if constexpr (VEC4) {
-#pragma unroll
-      for (int j = 0; j < K_ / 4; ++j) {
-        const float4 v = *reinterpret_cast<const float4*>(rowp + 4 * j);
-        R.xr[4 * j + 0] = v.x;
-        R.xr[4 * j + 1] = v.y;
-        R.xr[4 * j + 2] = v.z;
-        R.xr[4 * j + 3] = v.w;
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < K_; ++k) R.xr[k] = rowp[k];
-    }
-    R.t = Tg[(size_t)s * B_ + mr];
-    const float* cp = colp + (size_t)s * cstep;
-#pragma unroll
-    for (int i = 0; i < B_; ++i) R.xc[i] = cp[i * K_];
-  };
-
   float d_last = 0.f;
-  auto body = [&](CSet& R, int s) {
+  auto compute = [&](const LSet& V) {
+    CSet R;
+#pragma unroll
+    for (int k = 0; k < K_; ++k) R.xr[k] = V.xr[k / 4][k % 4];
+#pragma unroll
+    for (int i = 0; i < B_; ++i) R.xc[i] = V.xc[i / 4][i % 4];
+    R.t = V.t;
     // ---- forward: y = X @ w + b, k-ordered chain from +0 ----
     // rows 0/1 of wv reach every row that owns a batch row: rows 0..1 at
     // B_ = 32 (rows 2..3 run on copies of the bias, unused), all at 64
@@ -980,24 +1117,42 @@ k_toy_multistep_chain(const float* __restrict__ X,
       chain_bwd16<false>(g, p.hi, R.xc + 16);
     }
 
-    // this set's regs are dead from here: refill them for step s + D
-    prefetch(R, s + D);
-
     wv = wv - lr * g;
-    // compiler-only ordering point between steps (one wave, no LDS)
+    // compiler-only ordering point between steps
     __builtin_amdgcn_wave_barrier();
   };
 
-#pragma unroll
-  for (int j = 0; j < D; ++j) prefetch(ring[j], j);
-  int s = 0;
-  for (; s + D <= S; s += D) {
-#pragma unroll
-    for (int j = 0; j < D; ++j) body(ring[j], s + j);
+  // Step s lives in slot s mod 2H. `slot` is the slot of the next step to
+  // fetch; entering a ring half (slot 0 or H) means entering a new chunk,
+  // which is where the chunk's barrier goes.
+  int slot = 0;
+  int togo = 0;  // steps left to fetch in the current ring half
+  const int slots = 2 * H;
+  auto fetch_step = [&](LSet& R, int s) {
+    if (s < S) {
+      if (togo == 0) {
+        __syncthreads();
+        togo = H;
+      }
+      --togo;
+      fetch(R, slot);
+      slot = (slot + 1 == slots) ? 0 : slot + 1;
+    }
+  };
+  // Step s + 1 is fetched while step s computes: even steps through setA,
+  // odd steps through setB.
+  asm volatile("" : "+v"(wv));  // the param load's wait, out of the loop
+  fetch_step(setA, 0);
+  for (int s = 0; s < S; s += 2) {
+    settle(setA);
+    fetch_step(setB, s + 1);
+    compute(setA);  // step s
+    if (s + 1 < S) {
+      settle(setB);
+      fetch_step(setA, s + 2);
+      compute(setB);  // step s + 1
+    }
   }
-#pragma unroll
-  for (int j = 0; j < D - 1; ++j)
-    if (s + j < S) body(ring[j], s + j);
 
   if (lane < K_) param[w_off + lane] = wv;
   if (lane == K_) param[b_off] = wv;
@@ -1053,42 +1208,35 @@ std::string get_toy_multistep_impl() {
 }
 void set_toy_multistep_chain_depth(int64_t depth) {
   TORCH_CHECK(depth == 0 || (depth >= 2 && depth <= 4),
-              "chain prefetch depth must be 0 (default), 2, 3 or 4");
+              "chain ring depth (steps per ring half) must be 0 (default), "
+              "2, 3 or 4");
   g_chain_depth.store((int)depth);
 }
 
-// Measured on fresh tiles at batch 32 (profiles r03c), D = 2 / 3 / 4:
-// S = 1024 -> 281 / 282 / 281 ns/step, S = 64 -> 304 / 306 / 307. Depth no
-// longer pays (with the readlane broadcasts it was 335 / 329 / 319), so the
-// default is the smallest ring: 129 VGPRs instead of 254.
-static constexpr int kChainDefaultDepth = 2;
+// The chain depth is H, the steps per ring half (one barrier per H steps),
+// a runtime kernel argument clamped to what 64 KB of LDS holds (5 at batch
+// 32, 2 at batch 64). Measured at batch 32 (profiles r03d), H = 2 / 3 / 4:
+// S = 1024 -> 233 / 233 / 232 ns/step, S = 64 -> 267 / 270 / 273 (a launch
+// cannot start before its first H tiles are staged), so the default is the
+// smallest ring. One loader wave reaches the never-waiting ceiling at batch
+// 32; batch 64 gains 1.4% from a second one and nothing from a third.
+static constexpr int kChainDefaultH = 2;
+static constexpr int kChainLoaderWaves32 = 1;
+static constexpr int kChainLoaderWaves64 = 2;
 
 template <int B_>
 static void launch_toy_multistep_chain(const float* xp, const float* tp,
                                        float* pp, float* lossp, bool use_mse,
                                        int w_off, int b_off, float lr, int S) {
-  int depth = g_chain_depth.load();
-  if (depth == 0) depth = kChainDefaultDepth;
-  // rows are 80 B, so every row start is 16-byte aligned iff the base is
-  const bool vec4 = (reinterpret_cast<uintptr_t>(xp) & 15u) == 0;
-  auto go = [&](auto kptr) {
-    hipLaunchKernelGGL(kptr, dim3(1), dim3(64), 0, cur_stream(), xp, tp, pp,
-                       lossp, S, use_mse ? 1 : 0, w_off, b_off, lr);
-  };
-  auto by_depth = [&](auto vec) {
-    constexpr bool V = decltype(vec)::value;
-    if constexpr (B_ == 64) {
-      // 85 operand registers per set: a third set still needs AGPR copies
-      // (293 registers), and depth stopped paying at batch 32 anyway
-      go(k_toy_multistep_chain<64, 20, 2, V>);
-    } else {
-      if (depth == 2) go(k_toy_multistep_chain<B_, 20, 2, V>);
-      else if (depth == 3) go(k_toy_multistep_chain<B_, 20, 3, V>);
-      else go(k_toy_multistep_chain<B_, 20, 4, V>);
-    }
-  };
-  if (vec4) by_depth(std::true_type{});
-  else by_depth(std::false_type{});
+  constexpr int kMaxH = ChainSlot<B_, 20>::kMaxH;
+  static_assert(kMaxH >= 2, "the ring needs two steps per half");
+  int H = g_chain_depth.load();
+  if (H == 0) H = kChainDefaultH;
+  if (H > kMaxH) H = kMaxH;
+  constexpr int NL = B_ == 64 ? kChainLoaderWaves64 : kChainLoaderWaves32;
+  hipLaunchKernelGGL((k_toy_multistep_chain<B_, 20, NL>), dim3(1),
+                     dim3(64 * (1 + NL)), 0, cur_stream(), xp, tp, pp, lossp,
+                     S, H, use_mse ? 1 : 0, w_off, b_off, lr);
 }
 
 // fn(integral_constant<int, B>) for the two fast-path batch sizes
