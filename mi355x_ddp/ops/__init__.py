@@ -2,7 +2,8 @@
 
 Every op has two paths:
 - device tensors -> the hand-written CDNA4 HIP kernels in `mi355x_ddp._C`
-  (MFMA-tiled linear, CE/MSE, fused SGD, bucket copies). If the extension
+  (MFMA-tiled linear, CE/MSE, fused SGD / momentum SGD / AdamW, bucket
+  copies). If the extension
   is missing on a GPU host this layer raises — there is NO silent eager
   fallback on the GPU.
 - CPU tensors -> plain PyTorch reference implementations, used by the
@@ -151,6 +152,140 @@ def sgd_flat_(param_flat: torch.Tensor, grad_flat: torch.Tensor, lr: float,
         param_flat.add_(grad_flat, alpha=-lr)
         if zero_grad:
             grad_flat.zero_()
+
+
+def _expand_mask(decay_mask: torch.Tensor, numel: int) -> torch.Tensor:
+    """One byte per 4-element group -> one bool per element."""
+    return decay_mask.to(torch.bool).repeat_interleave(4)[:numel]
+
+
+def sgd_momentum_flat_(param_flat: torch.Tensor, grad_flat: torch.Tensor,
+                       buf: Optional[torch.Tensor], lr: float,
+                       momentum: float = 0.0, weight_decay: float = 0.0,
+                       nesterov: bool = False,
+                       zero_grad: bool = True) -> None:
+    """torch.optim.SGD's update (no dampening) over a flat bucket, grad
+    zeroing folded in:
+
+        d = g + wd*p;  buf = mu*buf + d;  d = nesterov ? d + mu*buf : buf
+        p -= lr*d;     g = 0 when zero_grad
+
+    `buf` is fp32 whatever the parameter dtype and starts at zero, which
+    reproduces torch's first-step `buf = d` with no step count. `buf=None`
+    requires momentum 0 (weight decay only). bf16 parameters: arithmetic in
+    fp32, ONE round-to-nearest on the parameter store; there are no fp32
+    master weights (as with sgd_flat_).
+
+    The CPU path is the same operation sequence as torch's single-tensor
+    SGD, in fp32; it is the numerics reference for the kernel."""
+    if buf is None and (momentum != 0 or nesterov):
+        raise ValueError("sgd_momentum_flat_: momentum needs a buffer")
+    if param_flat.is_cuda:
+        ext().sgd_momentum_flat(param_flat, grad_flat, buf, lr, momentum,
+                                weight_decay, nesterov, zero_grad)
+        return
+    sgd_momentum_reference_(param_flat, grad_flat, buf, lr, momentum,
+                            weight_decay, nesterov)
+    if zero_grad:
+        grad_flat.zero_()
+
+
+def sgd_momentum_reference_(p: torch.Tensor, g: torch.Tensor,
+                            buf: Optional[torch.Tensor], lr: float,
+                            momentum: float, weight_decay: float,
+                            nesterov: bool) -> None:
+    """The momentum-SGD update in plain torch ops, fp32 arithmetic, any
+    shape and device: torch's single-tensor SGD operation for operation."""
+    low = p.dtype != torch.float32
+    pf = p.float() if low else p
+    d = g.float() if low else g
+    if weight_decay != 0:
+        d = d.add(pf, alpha=weight_decay)
+    if buf is not None:
+        buf.mul_(momentum).add_(d)
+        d = d.add(buf, alpha=momentum) if nesterov else buf
+    pf.add_(d, alpha=-lr)
+    if low:
+        p.copy_(pf)
+
+
+def adamw_tick_(step_state: torch.Tensor, lr: float, beta1: float,
+                beta2: float) -> None:
+    """Advance the optimizer's step count by one: `step_state` is int32[4],
+    [0] the count t, [1]/[2] the fp32 bits of -(lr/(1-beta1^t)) and
+    1/sqrt(1-beta2^t) that `adamw_flat_` reads on the device. Called ONCE per
+    optimizer step, ahead of the per-bucket updates; on the GPU it is a
+    one-thread kernel, so a captured graph advances the count on replay."""
+    if step_state.is_cuda:
+        ext().adamw_tick(step_state, lr, beta1, beta2)
+    else:
+        step_state[0] += 1
+
+
+def adamw_flat_(param_flat: torch.Tensor, grad_flat: torch.Tensor,
+                exp_avg: torch.Tensor, exp_avg_sq: torch.Tensor,
+                step, lr: float, beta1: float, beta2: float, eps: float,
+                weight_decay: float,
+                decay_mask: Optional[torch.Tensor] = None,
+                zero_grad: bool = True) -> None:
+    """torch.optim.AdamW's update over a flat bucket at step count t, grad
+    zeroing folded in:
+
+        p *= 1 - lr*wd                     (where decay_mask allows)
+        m = b1*m + (1-b1)*g;  v = b2*v + (1-b2)*g*g
+        p -= (lr/(1-b1^t)) * m / (sqrt(v)/sqrt(1-b2^t) + eps)
+
+    weight_decay=0 is plain Adam. `decay_mask` is uint8 with one byte per
+    4-element group (the reducer aligns every parameter to 4 elements, so a
+    group never straddles two); a zero byte exempts the group from decay.
+    State is fp32 whatever the parameter dtype. bf16 parameters: arithmetic
+    in fp32, ONE round-to-nearest on the parameter store; there are no fp32
+    master weights.
+
+    `step`: on the GPU the int32 device tensor that `adamw_tick_` has
+    ALREADY advanced for this step (the kernel never sees a host count, so
+    the step is graph-capturable); on the CPU a Python int, the t of this
+    step. The CPU path is the same operation sequence as torch's
+    single-tensor AdamW on the CPU, in fp32; it is the numerics reference
+    for the kernel, which follows torch's DEVICE kernels instead (three
+    roundings placed differently: a few ulps)."""
+    if param_flat.is_cuda:
+        ext().adamw_flat(param_flat, grad_flat, exp_avg, exp_avg_sq, step,
+                         lr, beta1, beta2, eps, weight_decay, decay_mask,
+                         zero_grad)
+        return
+    adamw_reference_(param_flat, grad_flat, exp_avg, exp_avg_sq, int(step),
+                     lr, beta1, beta2, eps, weight_decay,
+                     None if decay_mask is None
+                     else _expand_mask(decay_mask, param_flat.numel()))
+    if zero_grad:
+        grad_flat.zero_()
+
+
+def adamw_reference_(p: torch.Tensor, g: torch.Tensor, exp_avg: torch.Tensor,
+                     exp_avg_sq: torch.Tensor, t: int, lr: float,
+                     beta1: float, beta2: float, eps: float,
+                     weight_decay: float,
+                     decays: Optional[torch.Tensor] = None) -> None:
+    """The AdamW update at step count t in plain torch ops, fp32
+    arithmetic, any shape and device: torch's single-tensor AdamW operation
+    for operation. `decays`: optional bool tensor of p's shape, False where
+    the weight decay is skipped."""
+    low = p.dtype != torch.float32
+    pf = p.float() if low else p
+    gf = g.float() if low else g
+    if weight_decay != 0:
+        if decays is None:
+            pf.mul_(1 - lr * weight_decay)
+        else:
+            pf.copy_(torch.where(decays, pf * (1 - lr * weight_decay), pf))
+    exp_avg.lerp_(gf, 1 - beta1)
+    exp_avg_sq.mul_(beta2).addcmul_(gf, gf, value=1 - beta2)
+    step_size = lr / (1 - beta1 ** t)
+    denom = (exp_avg_sq.sqrt() / (1 - beta2 ** t) ** 0.5).add_(eps)
+    pf.addcdiv_(exp_avg, denom, value=-step_size)
+    if low:
+        p.copy_(pf)
 
 
 def perm_index(seed: int, p: int, n: int) -> int:

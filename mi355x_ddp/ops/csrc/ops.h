@@ -1,7 +1,7 @@
 // Host-side launcher declarations for the MI355X (gfx950) kernel pack.
-// Implementations in kernels.hip and, for the toy training-step family
-// (toy_fused_fwd_bwd, toy_multistep*), toy_kernels.hip; bound to Python in
-// bindings.hip.
+// Implementations in kernels.hip, for the toy training-step family
+// (toy_fused_fwd_bwd, toy_multistep*) toy_kernels.hip, and for the stateful
+// flat-bucket optimizers optim_kernels.hip; bound to Python in bindings.hip.
 #pragma once
 #include <torch/extension.h>
 #include <cstdint>
@@ -48,6 +48,32 @@ torch::Tensor mse_bwd(torch::Tensor y, torch::Tensor t, double grad_scale,
 // kernel (folds reference optimizer.step() + zero_grad, single_gpu.py:22,26).
 void sgd_flat(torch::Tensor param_flat, torch::Tensor grad_flat,
               double lr, bool zero_grad);
+
+// Momentum SGD over a flat bucket (optim_kernels.hip), torch.optim.SGD's
+// formula without dampening:
+//   d = g + wd*p; buf = mu*buf + d; d = nesterov ? d + mu*buf : buf;
+//   p -= lr*d; g = 0 when zero_grad.
+// buf is f32 of the bucket's length whatever the parameter dtype and starts
+// at zero (which reproduces torch's first-step buf = d); without a buf the
+// momentum must be 0 (weight decay only).
+void sgd_momentum_flat(torch::Tensor param_flat, torch::Tensor grad_flat,
+                       c10::optional<torch::Tensor> buf, double lr,
+                       double momentum, double weight_decay, bool nesterov,
+                       bool zero_grad);
+
+// AdamW over a flat bucket with the step count on the device, so that a
+// captured graph advances it on replay. step_state is int32[4]:
+// [0] the step t, [1]/[2] the f32 bits of -(lr/(1-b1^t)) and 1/sqrt(1-b2^t).
+// adamw_tick advances it ONCE per optimizer step, ahead of the per-bucket
+// adamw_flat launches on the same stream, which only read it.
+// decay_mask: optional uint8, one byte per 4-element group; 0 = no decay.
+void adamw_tick(torch::Tensor step_state, double lr, double beta1,
+                double beta2);
+void adamw_flat(torch::Tensor param_flat, torch::Tensor grad_flat,
+                torch::Tensor exp_avg, torch::Tensor exp_avg_sq,
+                torch::Tensor step_state, double lr, double beta1,
+                double beta2, double eps, double weight_decay,
+                c10::optional<torch::Tensor> decay_mask, bool zero_grad);
 
 // Bucket gather/scatter ("flatten/unflatten"): one launch
 // moves every listed tensor <-> its segment of the flat bucket.

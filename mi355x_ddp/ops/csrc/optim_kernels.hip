@@ -1,0 +1,281 @@
+// Stateful optimizers over one flat bucket: momentum SGD and AdamW.
+//
+// Both are memory-bound streaming kernels in the layout of k_sgd_flat_*:
+// 4 elements per lane (one float4, or one ushort4 of bf16), a grid capped
+// at kMaxBlocks with a grid-stride loop (guide G11), int64 indexing.
+// Parameters and gradients are f32 or bf16; optimizer state is always f32.
+// bf16 does the arithmetic in f32 and rounds to nearest once, on the
+// parameter store — there are no f32 master weights.
+//
+// Rounding follows torch's single-tensor optimizers as they run ON THE
+// DEVICE, operation by operation, so that a model moved from torch.optim to
+// these kernels keeps its trajectory bit for bit: a fused multiply-add
+// exactly where torch's device add(alpha)/lerp/addcmul/addcdiv kernels
+// contract one, separate roundings everywhere else, IEEE divide and sqrt,
+// the division by the scalar sqrt(bc2) as a multiplication by its
+// reciprocal. (torch's CPU kernels, which ops.sgd_momentum_flat_ /
+// ops.adamw_flat_ mirror on the host, place three of AdamW's roundings
+// differently; momentum SGD is the same sequence on both.) Contraction is
+// therefore switched off for the file and every fma below is explicit.
+//
+// Bucket padding (p == g == 0, state 0) stays exactly 0 under both kernels:
+// every term of both updates is a product with p, g or the state.
+#include "kernel_common.h"
+#include "ops.h"
+
+#pragma clang fp contract(off)
+
+namespace mi355x {
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kMaxBlocks = 2048;
+
+struct F4 {
+  float v[4];
+};
+
+__device__ __forceinline__ F4 ld4(const float* p, int64_t i) {
+  const float4 t = reinterpret_cast<const float4*>(p)[i];
+  return {{t.x, t.y, t.z, t.w}};
+}
+__device__ __forceinline__ F4 ld4(const __hip_bfloat16* p, int64_t i) {
+  const ushort4 t = reinterpret_cast<const ushort4*>(p)[i];
+  return {{__uint_as_float((uint32_t)t.x << 16),
+           __uint_as_float((uint32_t)t.y << 16),
+           __uint_as_float((uint32_t)t.z << 16),
+           __uint_as_float((uint32_t)t.w << 16)}};
+}
+__device__ __forceinline__ void st4(float* p, int64_t i, const F4& f) {
+  reinterpret_cast<float4*>(p)[i] =
+      make_float4(f.v[0], f.v[1], f.v[2], f.v[3]);
+}
+__device__ __forceinline__ unsigned short bf16_bits(float f) {
+  const __hip_bfloat16 h = __float2bfloat16(f);  // round to nearest even
+  return *reinterpret_cast<const unsigned short*>(&h);
+}
+__device__ __forceinline__ void st4(__hip_bfloat16* p, int64_t i,
+                                    const F4& f) {
+  reinterpret_cast<ushort4*>(p)[i] =
+      make_ushort4(bf16_bits(f.v[0]), bf16_bits(f.v[1]), bf16_bits(f.v[2]),
+                   bf16_bits(f.v[3]));
+}
+__device__ __forceinline__ void zero4(float* p, int64_t i) {
+  reinterpret_cast<float4*>(p)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+__device__ __forceinline__ void zero4(__hip_bfloat16* p, int64_t i) {
+  reinterpret_cast<ushort4*>(p)[i] = make_ushort4(0, 0, 0, 0);
+}
+
+}  // namespace
+
+// d = g + wd*p; buf = mu*buf + d; d = nesterov ? d + mu*buf : buf;
+// p -= lr*d. buf == nullptr is momentum 0 (weight decay only).
+template <typename T>
+__global__ void __launch_bounds__(kThreads)
+k_sgd_momentum_flat(T* __restrict__ p, T* __restrict__ g,
+                    float* __restrict__ buf, float neg_lr, float mu, float wd,
+                    int nesterov, int zero, int64_t n4) {
+  const int64_t stride = (int64_t)gridDim.x * kThreads;
+  for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n4;
+       i += stride) {
+    F4 pv = ld4(p, i);
+    const F4 gv = ld4(g, i);
+    F4 bv = {{0.f, 0.f, 0.f, 0.f}};
+    if (buf) bv = ld4(buf, i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float d = gv.v[j];
+      if (wd != 0.f) d = __builtin_fmaf(pv.v[j], wd, d);
+      if (buf) {
+        const float b = bv.v[j] * mu + d;
+        bv.v[j] = b;
+        d = nesterov ? __builtin_fmaf(b, mu, d) : b;
+      }
+      pv.v[j] = __builtin_fmaf(d, neg_lr, pv.v[j]);
+    }
+    st4(p, i, pv);
+    if (buf) st4(buf, i, bv);
+    if (zero) zero4(g, i);
+  }
+}
+
+// Advances the device-resident step count and derives the two bias-
+// correction scalars the bucket kernels need, in double so they round to
+// the same f32 as torch's Python-double values:
+//   state[0] = t (int32), state[1] = bits of -(lr / (1 - b1^t)),
+//   state[2] = bits of 1 / sqrt(1 - b2^t).
+// One thread, launched once per optimizer step AHEAD of the bucket
+// kernels on the same stream: no bucket block can see a half-advanced
+// count, and a captured graph replays the increment.
+__global__ void k_adamw_tick(int32_t* __restrict__ state, double lr,
+                             double beta1, double beta2) {
+  const int32_t t = state[0] + 1;
+  const double bc1 = 1.0 - pow(beta1, (double)t);
+  const double bc2 = 1.0 - pow(beta2, (double)t);
+  state[0] = t;
+  state[1] = __float_as_int((float)(-(lr / bc1)));
+  state[2] = __float_as_int((float)(1.0 / sqrt(bc2)));
+}
+
+// torch's AdamW step (decoupled decay), t and the bias corrections read
+// from `state`:
+//   p *= 1 - lr*wd             (groups whose mask byte is non-zero)
+//   m += (1-b1) * (g - m)      (lerp, as torch computes b1*m + (1-b1)*g)
+//   v  = b2*v + (1-b2)*g*g
+//   p += -(lr/bc1) * (m / (sqrt(v) * (1/sqrt(bc2)) + eps))
+// mask: one byte per 4-element group (== per lane), nullptr = decay all.
+template <typename T>
+__global__ void __launch_bounds__(kThreads)
+k_adamw_flat(T* __restrict__ p, T* __restrict__ g, float* __restrict__ m,
+             float* __restrict__ v, const int32_t* __restrict__ state,
+             float decay, float w1, float beta2, float w2, float eps,
+             const uint8_t* __restrict__ mask, int zero, int64_t n4) {
+  const float neg_step = __int_as_float(state[1]);
+  const float inv_bc2_sqrt = __int_as_float(state[2]);
+  const int64_t stride = (int64_t)gridDim.x * kThreads;
+  for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n4;
+       i += stride) {
+    F4 pv = ld4(p, i);
+    const F4 gv = ld4(g, i);
+    F4 mv = ld4(m, i);
+    F4 vv = ld4(v, i);
+    const bool decays = decay != 1.f && (mask == nullptr || mask[i] != 0);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float gj = gv.v[j];
+      float pj = pv.v[j];
+      if (decays) pj = pj * decay;
+      // torch's lerp picks the form by weight: m + w*(g-m) below 0.5,
+      // g - (g-m)*(1-w) from there on
+      const float mj = w1 < 0.5f
+                           ? __builtin_fmaf(w1, gj - mv.v[j], mv.v[j])
+                           : __builtin_fmaf(w1 - 1.f, gj - mv.v[j], gj);
+      const float vj = __builtin_fmaf(w2, gj * gj, vv.v[j] * beta2);
+      const float denom = sqrtf(vj) * inv_bc2_sqrt + eps;
+      pv.v[j] = __builtin_fmaf(neg_step, mj / denom, pj);
+      mv.v[j] = mj;
+      vv.v[j] = vj;
+    }
+    st4(p, i, pv);
+    st4(m, i, mv);
+    st4(v, i, vv);
+    if (zero) zero4(g, i);
+  }
+}
+
+namespace {
+
+int64_t check_flat(const torch::Tensor& param, const torch::Tensor& grad,
+                   const char* name) {
+  TORCH_CHECK(param.is_cuda() && grad.is_cuda(), name,
+              ": flat buffers must be device tensors");
+  TORCH_CHECK(param.is_contiguous() && grad.is_contiguous(), name,
+              ": flat buffers must be contiguous");
+  TORCH_CHECK(grad.scalar_type() == param.scalar_type() &&
+                  grad.numel() == param.numel() &&
+                  grad.device() == param.device(),
+              name, ": grad must match param in dtype, length and device");
+  TORCH_CHECK(param.numel() % 4 == 0, name,
+              ": bucket length must be padded to a multiple of 4");
+  // one 4-element vector access per lane: 16 B (f32) / 8 B (bf16) aligned
+  const uintptr_t align = 4 * param.element_size();
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(param.data_ptr()) % align == 0 &&
+                  reinterpret_cast<uintptr_t>(grad.data_ptr()) % align == 0,
+              name, ": flat buffers must be aligned to 4 elements");
+  return param.numel() / 4;
+}
+
+void check_state(const torch::Tensor& s, const torch::Tensor& param,
+                 const char* name, const char* what) {
+  TORCH_CHECK(s.is_cuda() && s.is_contiguous() &&
+                  s.scalar_type() == at::kFloat &&
+                  s.numel() == param.numel() &&
+                  s.device() == param.device() &&
+                  reinterpret_cast<uintptr_t>(s.data_ptr()) % 16 == 0,
+              name, ": ", what,
+              " must be a contiguous, 16 B aligned f32 device tensor of the "
+              "bucket's length");
+}
+
+dim3 flat_grid(int64_t n4) {
+  const int64_t blocks = (n4 + kThreads - 1) / kThreads;
+  return dim3((unsigned)std::min<int64_t>(std::max<int64_t>(blocks, 1),
+                                          kMaxBlocks));
+}
+
+}  // namespace
+
+void sgd_momentum_flat(torch::Tensor param_flat, torch::Tensor grad_flat,
+                       c10::optional<torch::Tensor> buf, double lr,
+                       double momentum, double weight_decay, bool nesterov,
+                       bool zero_grad) {
+  const int64_t n4 = check_flat(param_flat, grad_flat, "sgd_momentum_flat");
+  float* bp = nullptr;
+  if (buf.has_value() && buf->defined()) {
+    check_state(*buf, param_flat, "sgd_momentum_flat", "buf");
+    bp = buf->data_ptr<float>();
+  }
+  TORCH_CHECK(bp != nullptr || (momentum == 0.0 && !nesterov),
+              "sgd_momentum_flat: momentum needs a buffer");
+  if (n4 == 0) return;
+  DISPATCH_F32_BF16(param_flat.scalar_type(), "sgd_momentum_flat", {
+    hipLaunchKernelGGL((k_sgd_momentum_flat<scalar_t>), flat_grid(n4),
+                       dim3(kThreads), 0, cur_stream(),
+                       dptr<scalar_t>(param_flat), dptr<scalar_t>(grad_flat),
+                       bp, (float)(-lr), (float)momentum, (float)weight_decay,
+                       nesterov ? 1 : 0, zero_grad ? 1 : 0, n4);
+  });
+  HIP_OK(hipGetLastError());
+}
+
+void adamw_tick(torch::Tensor step_state, double lr, double beta1,
+                double beta2) {
+  TORCH_CHECK(step_state.is_cuda() && step_state.is_contiguous() &&
+                  step_state.scalar_type() == at::kInt &&
+                  step_state.numel() >= 3,
+              "adamw_tick: step_state must be an int32 device tensor [>=3]");
+  hipLaunchKernelGGL(k_adamw_tick, dim3(1), dim3(1), 0, cur_stream(),
+                     step_state.data_ptr<int32_t>(), lr, beta1, beta2);
+  HIP_OK(hipGetLastError());
+}
+
+void adamw_flat(torch::Tensor param_flat, torch::Tensor grad_flat,
+                torch::Tensor exp_avg, torch::Tensor exp_avg_sq,
+                torch::Tensor step_state, double lr, double beta1,
+                double beta2, double eps, double weight_decay,
+                c10::optional<torch::Tensor> decay_mask, bool zero_grad) {
+  const int64_t n4 = check_flat(param_flat, grad_flat, "adamw_flat");
+  check_state(exp_avg, param_flat, "adamw_flat", "exp_avg");
+  check_state(exp_avg_sq, param_flat, "adamw_flat", "exp_avg_sq");
+  TORCH_CHECK(step_state.is_cuda() && step_state.is_contiguous() &&
+                  step_state.scalar_type() == at::kInt &&
+                  step_state.numel() >= 3 &&
+                  step_state.device() == param_flat.device(),
+              "adamw_flat: step_state must be an int32 device tensor [>=3]");
+  const uint8_t* mp = nullptr;
+  if (decay_mask.has_value() && decay_mask->defined()) {
+    TORCH_CHECK(decay_mask->is_cuda() && decay_mask->is_contiguous() &&
+                    decay_mask->scalar_type() == at::kByte &&
+                    decay_mask->numel() == n4 &&
+                    decay_mask->device() == param_flat.device(),
+                "adamw_flat: decay_mask must be a uint8 device tensor with "
+                "one byte per 4-element group");
+    mp = decay_mask->data_ptr<uint8_t>();
+  }
+  if (n4 == 0) return;
+  DISPATCH_F32_BF16(param_flat.scalar_type(), "adamw_flat", {
+    hipLaunchKernelGGL((k_adamw_flat<scalar_t>), flat_grid(n4),
+                       dim3(kThreads), 0, cur_stream(),
+                       dptr<scalar_t>(param_flat), dptr<scalar_t>(grad_flat),
+                       exp_avg.data_ptr<float>(), exp_avg_sq.data_ptr<float>(),
+                       step_state.data_ptr<int32_t>(),
+                       (float)(1.0 - lr * weight_decay), (float)(1.0 - beta1),
+                       (float)beta2, (float)(1.0 - beta2), (float)eps, mp,
+                       zero_grad ? 1 : 0, n4);
+  });
+  HIP_OK(hipGetLastError());
+}
+
+}  // namespace mi355x

@@ -1,43 +1,64 @@
-"""FusedSGD: momentum-less SGD matching the reference's
-torch.optim.SGD(lr=1e-3) (single_gpu.py:51), fused over the reducer's flat
-buckets when the model is engine-wrapped.
+"""FusedSGD: torch.optim.SGD's update (momentum, weight decay, nesterov; no
+dampening) fused over the reducer's flat buckets when the model is
+engine-wrapped. With the defaults it is the momentum-less SGD matching the
+reference's torch.optim.SGD(lr=1e-3) (single_gpu.py:51).
 
 - Bucketed params (marked by the Reducer): ONE hand-written HIP kernel per
-  bucket does p -= lr*g AND zeroes the flat grad (SURVEY §2.2 N8+N9 —
-  optimizer.step + zero_grad in one launch).
-- Un-bucketed params: plain per-parameter update (CPU plumbing path and
-  models trained without the DDP engine).
+  bucket does the update AND zeroes the flat grad (SURVEY §2.2 N8+N9 —
+  optimizer.step + zero_grad in one launch). momentum == weight_decay == 0
+  runs `k_sgd_flat_*` (p -= lr*g) and allocates no state; anything else
+  runs `k_sgd_momentum_flat`, its momentum buffer a flat fp32 buffer per
+  bucket.
+- Un-bucketed params: the same formula per parameter (CPU plumbing path
+  and models trained without the DDP engine).
+
+`state_dict()` interchanges with torch.optim.SGD over the same parameters
+(`momentum_buffer`, here always fp32). Limits: see flat_optim.py — single
+param_group when attached, host-scalar lr, no fp32 master weights for bf16.
 """
 
 from __future__ import annotations
 
-import os
 from typing import Iterable
 
 import torch
 
 from .. import ops
+from .flat_optim import FlatBucketOptimizer
 
 
-class FusedSGD(torch.optim.Optimizer):
-    def __init__(self, params: Iterable[torch.nn.Parameter], lr: float):
+class FusedSGD(FlatBucketOptimizer):
+    _state_keys = ("momentum_buffer",)
+
+    def __init__(self, params: Iterable[torch.nn.Parameter], lr: float,
+                 momentum: float = 0, dampening: float = 0,
+                 weight_decay: float = 0, nesterov: bool = False):
         if lr <= 0:
             raise ValueError(f"invalid lr {lr}")
-        super().__init__(params, dict(lr=lr))
-        self._flat_pairs = None  # bound by attach_reducer
+        if momentum < 0:
+            raise ValueError(f"invalid momentum {momentum}")
+        if weight_decay < 0:
+            raise ValueError(f"invalid weight_decay {weight_decay}")
+        if dampening != 0:
+            raise ValueError("FusedSGD does not support dampening "
+                             f"(got {dampening}); use torch.optim.SGD")
+        if nesterov and momentum <= 0:
+            raise ValueError(
+                "Nesterov momentum requires a momentum and zero dampening")
+        super().__init__(params, dict(lr=lr, momentum=momentum,
+                                      dampening=dampening,
+                                      weight_decay=weight_decay,
+                                      nesterov=nesterov))
 
-    def attach_reducer(self, reducer) -> None:
-        """Bind the reducer's flat (param, grad) pairs; step() then runs one
-        fused kernel per bucket instead of one update per parameter.
-        Requires a single param_group: the flat-bucket step applies ONE lr
-        to each bucket, and the per-group loop in step() would otherwise
-        re-apply every bucket once per group."""
-        if len(self.param_groups) != 1:
-            raise ValueError("FusedSGD.attach_reducer requires a single "
-                             "param_group (flat buckets take one lr)")
-        self._flat_pairs = reducer.flat_pairs()
-        self._bucketed = {id(p) for b in reducer.buckets for p in b.params}
-        self._reducer = reducer
+    def _stateful(self) -> bool:
+        return any(g["momentum"] != 0 for g in self.param_groups)
+
+    def _check_hyper(self) -> None:
+        for g in self.param_groups:
+            if g.get("dampening", 0) != 0:
+                raise ValueError("FusedSGD does not support dampening")
+            if g.get("maximize", False):
+                raise ValueError("FusedSGD does not support maximize")
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -45,38 +66,32 @@ class FusedSGD(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        # Stream-race assertion (MI355X_DEBUG_SYNC=1): the
-        # fused step reads flat_grad on the compute stream — if bucket
-        # collectives were launched but finalize() never fenced them, that
-        # read races the comm stream. Catch the protocol violation loudly
-        # instead of training on half-reduced gradients.
-        if (os.environ.get("MI355X_DEBUG_SYNC") == "1"
-                and getattr(self, "_reducer", None) is not None
-                and self._reducer.unfenced):
-            raise RuntimeError(
-                "FusedSGD.step() called while bucket all-reduces are "
-                "in flight and unfenced — call finalize_backward() (or "
-                "Reducer.finalize()) between loss.backward() and "
-                "optimizer.step()")
+        self._check_fenced()
         for group in self.param_groups:
-            lr = group["lr"]
+            lr, mu = group["lr"], group["momentum"]
+            wd, nesterov = group["weight_decay"], group["nesterov"]
+            if mu == 0 and wd == 0:
+                # the reference's plain SGD: one k_sgd_flat per bucket
+                if self._flat_pairs is not None:
+                    for flat_param, flat_grad in self._flat_pairs:
+                        ops.sgd_flat_(flat_param, flat_grad, lr,
+                                      zero_grad=True)
+                for p in self._loose_params(group):
+                    p.add_(p.grad, alpha=-lr)
+                continue
             if self._flat_pairs is not None:
-                for flat_param, flat_grad in self._flat_pairs:
-                    ops.sgd_flat_(flat_param, flat_grad, lr, zero_grad=True)
-                for p in group["params"]:
-                    if id(p) not in self._bucketed and p.grad is not None:
-                        p.add_(p.grad, alpha=-lr)
-            else:
-                for p in group["params"]:
-                    if p.grad is not None:
-                        p.add_(p.grad, alpha=-lr)
+                if mu != 0 and "momentum_buffer" not in self._flat_state:
+                    # momentum switched on after the attach
+                    self._bind_flat_state()
+                bufs = self._flat_state.get("momentum_buffer")
+                for bi, (flat_param, flat_grad) in enumerate(self._flat_pairs):
+                    ops.sgd_momentum_flat_(
+                        flat_param, flat_grad,
+                        bufs[bi] if mu != 0 else None, lr, mu, wd, nesterov,
+                        zero_grad=True)
+            for p in self._loose_params(group):
+                buf = self._param_state(p)["momentum_buffer"] \
+                    if mu != 0 else None
+                ops.sgd_momentum_reference_(p, p.grad, buf, lr, mu, wd,
+                                            nesterov)
         return loss
-
-    def zero_grad(self, set_to_none: bool = True):
-        if self._flat_pairs is not None:
-            # bucketed grads are zeroed by the fused step; nothing to do
-            # unless the user zeroes before the first step.
-            for _, flat_grad in self._flat_pairs:
-                flat_grad.zero_()
-            return
-        super().zero_grad(set_to_none=set_to_none)

@@ -12,7 +12,9 @@ it. The observable surface is preserved:
   rank-0 unwrapped state_dict (multigpu.py:53-56,61), snapshot dict
   {"MODEL_STATE", "EPOCHS_RUN"} -> snapshot.pt (multigpu_torchrun.py:57-62)
   restored pre-DDP-wrap (multigpu_torchrun.py:30-34), wrapped state ->
-  model_ddp.pth (multigpu_profile.py:76-78)
+  model_ddp.pth (multigpu_profile.py:76-78). An optimizer that keeps state
+  (momentum, Adam moments) adds an "OPTIMIZER_STATE" key to the snapshot;
+  a stateless one writes exactly the reference's two keys
 - resume loop `range(epochs_run, max_epochs)` (multigpu_torchrun.py:64-66)
 
 Reference warts intentionally fixed:
@@ -151,18 +153,19 @@ class Trainer:
         elif wrap_ddp and dist.is_available() and dist.is_initialized():
             # world 1 wraps too: the engine still provides flat buckets and
             # the fused SGD path (there is simply no communicator).
-            from .parallel import DDP, FusedSGD
+            from .parallel import DDP, FlatBucketOptimizer
             graphed = engine == "hooks-graph" and self.device.type == "cuda"
             self.model = DDP(self.model, bucket_cap_mb=bucket_cap_mb,
                              cpp_hooks=False if graphed else None)
             self._distributed = True
-            if isinstance(self.optimizer, FusedSGD):
+            if isinstance(self.optimizer, FlatBucketOptimizer):
                 self.optimizer.attach_reducer(self.model.reducer)
-            # A bucket-attached FusedSGD zeroes the flat grads inside its
-            # step kernel; any other optimizer needs an explicit zero or
-            # gradients would accumulate across steps.
+            # A bucket-attached flat optimizer (FusedSGD, FusedAdamW) zeroes
+            # the flat grads inside its step kernel; any other optimizer
+            # needs an explicit zero or gradients would accumulate across
+            # steps.
             self._needs_zero = not (
-                isinstance(self.optimizer, FusedSGD)
+                isinstance(self.optimizer, FlatBucketOptimizer)
                 and self.optimizer._flat_pairs is not None)
             if engine == "hooks-graph" and self.device.type == "cuda" \
                     and not (self._autocast or self._nhwc):
@@ -180,8 +183,10 @@ class Trainer:
 
     def _try_fast_engine(self, kind: str) -> bool:
         """Engage the toy fast path when the configuration qualifies:
-        HipLinear(K,1) model, MSE loss, FusedSGD with a single lr, CUDA
-        device. Returns False (caller keeps the hooks path) otherwise."""
+        HipLinear(K,1) model, MSE loss, plain FusedSGD (no momentum, no
+        weight decay — the toy kernels apply p -= lr*g and nothing else)
+        with a single lr, CUDA device. Returns False (caller keeps the
+        hooks path) otherwise."""
         import torch.distributed as dist
         from .models.toy import HipLinear
         from .parallel import FusedSGD
@@ -191,7 +196,9 @@ class Trainer:
                 and self.device.type == "cuda"
                 and self.loss_fn is ops.mse_loss
                 and isinstance(self.optimizer, FusedSGD)
-                and len(self.optimizer.param_groups) == 1):
+                and len(self.optimizer.param_groups) == 1
+                and self.optimizer.param_groups[0]["momentum"] == 0
+                and self.optimizer.param_groups[0]["weight_decay"] == 0):
             return False
         if dist.is_available() and dist.is_initialized() \
                 and dist.get_world_size() > 1:
@@ -225,6 +232,8 @@ class Trainer:
         # keys MODEL_STATE / EPOCHS_RUN, multigpu_torchrun.py:57-62).
         snapshot = torch.load(snapshot_path, map_location=self.device, weights_only=True)
         self._unwrapped().load_state_dict(snapshot["MODEL_STATE"])
+        if "OPTIMIZER_STATE" in snapshot:
+            self.optimizer.load_state_dict(snapshot["OPTIMIZER_STATE"])
         self.epochs_run = snapshot["EPOCHS_RUN"]
         print(f"Resuming training from snapshot at Epoch {self.epochs_run}")
 
@@ -252,6 +261,10 @@ class Trainer:
             "MODEL_STATE": self._unwrapped().state_dict(),
             "EPOCHS_RUN": epoch,
         }
+        # a stateless optimizer keeps the reference's two-key format
+        opt_state = self.optimizer.state_dict()
+        if len(opt_state["state"]) > 0:
+            snapshot["OPTIMIZER_STATE"] = opt_state
         self._atomic_save(snapshot, self.snapshot_path)
         print(f"Epoch {epoch} | Training snapshot saved at {self.snapshot_path}")
 
