@@ -19,9 +19,13 @@
 // MI355X_TOY_MULTISTEP).
 //
 // Beyond parity (design notes in docs/KERNELS.md): the multi-step
-// trainers (`k_toy_multistep_spec`, `k_toy_multistep_bf16w`) run S
-// sequential SGD steps per launch with LDS-resident weights; their MESH
-// variants embed a per-step device-side xGMI all-reduce (p2p_mesh.h).
+// trainers (`k_toy_multistep_spec` for f32, `k_toy_multistep_bf16w` for
+// bf16) run S sequential SGD steps per launch with LDS-resident weights;
+// their MESH variants embed a per-step device-side xGMI all-reduce
+// (p2p_mesh.h).
+//
+// Order: the generic tile step, k_toy_fused, k_toy_multistep; mesh_exchange,
+// k_toy_multistep_spec, k_toy_multistep_bf16w; the chain kernel; the host.
 
 #include <hip/hip_runtime.h>
 
@@ -313,48 +317,50 @@ __global__ void k_toy_multistep(const T* __restrict__ X,
   if (lane == 0 && loss_out) *loss_out = use_mse ? loss_last / (float)B : 0.f;
 }
 
-// ---------------------------------------------------------------------------
-// Compile-time-shape multi-step trainer for the canonical toy shape.
-// All loop bounds are template constants so every MFMA operand lives in a
-// REGISTER, prefetched from global memory in operand layout during the
-// previous step's compute (the epoch shard is L2-resident after its
-// gather, so the depth-1 prefetch covers the latency). LDS is used only
-// where data must cross lanes: the w vector (updated by q==0 lanes, read
-// by r==0 lanes) and the per-row dY exchange between the forward readout
-// and the backward MFMA. Divisions are hoisted to one reciprocal
-// (2/B is exact for the reference batch 32, so dy is bitwise-unchanged).
+// Mesh arguments of the fast MFMA kernels; the defaults are the no-mesh
+// call. The kernels take them loose (in a by-value struct the pointers lose
+// __restrict__ and the MESH step loops gain loads) and bundle for
+// mesh_exchange.
+struct MeshArgs {
+  MeshSlot* const* peer_slots = nullptr;
+  MeshSlot* my_mb = nullptr;
+  int world = 1;
+  float inv_world = 1.f;
+  unsigned long long seq0 = 0;
+  unsigned int* err = nullptr;
+};
 
 // In-kernel mesh exchange for the multi-step trainers: scatter this
 // rank's 21-float gradient vector (held one value per q==0 lane per
-// K-tile, db on the free column) into every rank's mailbox, publish a
-// per-step sequence number, bounded-wait for all peers, and return the
+// K-tile, db on the free column) into every rank's mailbox, publish the
+// sequence number of step s, bounded-wait for all peers, and return the
 // averaged value for this lane's tile. Returns false on timeout (caller
 // must set the error flag and exit).
 template <int KT>
-__device__ __forceinline__ bool mesh_exchange(
-    float (&gval)[KT], int K_, int lane, int r, int q,
-    MeshSlot* const* __restrict__ peer_slots, MeshSlot* __restrict__ my_mb,
-    int mworld, float minv_world, unsigned long long sq) {
+__device__ __forceinline__ bool mesh_exchange(float (&gval)[KT], int K_,
+                                              int lane, int r, int q,
+                                              const MeshArgs& m, int s) {
+  const unsigned long long sq = m.seq0 + (unsigned long long)s;
   if (q == 0) {
 #pragma unroll
     for (int tk = 0; tk < KT; ++tk) {
       const int k = tk * 16 + r;
       if (k <= K_) {
-        for (int p = 0; p < mworld; ++p) peer_slots[p]->data[k] = gval[tk];
+        for (int p = 0; p < m.world; ++p) m.peer_slots[p]->data[k] = gval[tk];
       }
     }
   }
   __threadfence_system();
   __syncthreads();
   if (lane == 0) {
-    for (int p = 0; p < mworld; ++p)
-      __hip_atomic_store(&peer_slots[p]->seq, sq, __ATOMIC_RELEASE,
+    for (int p = 0; p < m.world; ++p)
+      __hip_atomic_store(&m.peer_slots[p]->seq, sq, __ATOMIC_RELEASE,
                          __HIP_MEMORY_SCOPE_SYSTEM);
   }
   bool timed_out = false;
-  if (lane < mworld) {
+  if (lane < m.world) {
     const unsigned long long t0c = __builtin_amdgcn_s_memrealtime();
-    while (__hip_atomic_load(&my_mb[lane].seq, __ATOMIC_ACQUIRE,
+    while (__hip_atomic_load(&m.my_mb[lane].seq, __ATOMIC_ACQUIRE,
                              __HIP_MEMORY_SCOPE_SYSTEM) < sq) {
       if (__builtin_amdgcn_s_memrealtime() - t0c > 500000000ull) {
         timed_out = true;
@@ -374,12 +380,204 @@ __device__ __forceinline__ bool mesh_exchange(
       const int k = tk * 16 + r;
       if (k <= K_) {
         float sum = 0.f;
-        for (int p = 0; p < mworld; ++p) sum += my_mb[p].data[k];
-        gval[tk] = sum * minv_world;
+        for (int p = 0; p < m.world; ++p) sum += m.my_mb[p].data[k];
+        gval[tk] = sum * m.inv_world;
       }
     }
   }
   return true;
+}
+
+// ---------------------------------------------------------------------------
+// Compile-time-shape f32 multi-step trainer for the canonical toy shape.
+// All loop bounds are template constants so every MFMA operand lives in a
+// REGISTER, prefetched from global memory in operand layout during the
+// previous step's compute (the epoch shard is L2-resident after its
+// gather, so the depth-1 prefetch covers the latency). LDS is used only
+// where data must cross lanes: the w vector (updated by q==0 lanes, read
+// by r==0 lanes) and the per-row dY exchange between the forward readout
+// and the backward MFMA.
+// ---------------------------------------------------------------------------
+template <int B_, int K_, bool MESH = false>
+__global__ void __launch_bounds__(64, 1)
+k_toy_multistep_spec(const float* __restrict__ X, const float* __restrict__ Tg,
+                     float* __restrict__ param, float* __restrict__ loss_out,
+                     int S, int use_mse, int w_off, int b_off, float lr,
+                     MeshSlot* const* __restrict__ peer_slots,
+                     MeshSlot* __restrict__ my_mb, int mworld,
+                     float minv_world, unsigned long long seq0,
+                     unsigned int* __restrict__ mesh_err) {
+  static_assert(B_ % 16 == 0, "whole 16-row tiles: rows carry no guards");
+  constexpr int MT = B_ / 16;          // fwd 16-row tiles
+  constexpr int KT = (K_ + 15) / 16;   // bwd 16-col tiles
+  constexpr int KS = (K_ + 3) / 4;     // fwd k-steps
+  constexpr int BS = B_ / 4;           // bwd i-steps
+  const int lane = threadIdx.x;
+  const int r = lane & 15, q = lane >> 4;
+  __shared__ float ws[33];             // w (K_) + bias at ws[32]
+  __shared__ float dy_s[B_];
+
+  if (lane < K_) ws[lane] = param[w_off + lane];
+  if (lane == K_) ws[32] = param[b_off];
+  const float inv2B = 2.f / (float)B_;
+  // updater lanes (q==0) also keep their w values in registers so the
+  // end-of-iteration update is WRITE-only to LDS (no dependent LDS read
+  // on the critical path); readers still take w from LDS
+  float wreg[KT];
+#pragma unroll
+  for (int tk = 0; tk < KT; ++tk) {
+    const int k = tk * 16 + r;
+    wreg[tk] = (k < K_) ? param[w_off + ((k < K_) ? k : 0)] : 0.f;
+  }
+
+  // Per-lane operand registers, software-pipelined: `c*` hold the step
+  // being computed and receive the next step's loads as soon as they are
+  // dead (see below). Loads are raw (address-clamped, no value select):
+  // lanes with k >= K_ load in-bounds garbage whose products are either
+  // multiplied by a zeroed LDS-side operand (wv) or discarded by the
+  // guarded ws writes — so no per-load mask, and therefore no vmcnt wait
+  // until the next iteration's first MFMA use. (Ternary-guarded loads
+  // compile to exec-masked branch-per-element code that serializes the
+  // burst, seen in the r01b ISA.)
+  float cfA[MT][KS];  // fwd A: X[tm*16+r][4*kk+q]
+  float cbB[KT][BS];  // bwd B: X[4*ii+q][tk*16+r]
+  float ctR[MT][4];   // targets for rows tm*16+q*4+i
+
+  auto prefetch = [&](int s) {
+    const float* Xs = X + (size_t)s * (B_ * K_);
+    const float* Ts = Tg + (size_t)s * B_;
+#pragma unroll
+    for (int tm = 0; tm < MT; ++tm) {
+      const int m = tm * 16 + r;
+#pragma unroll
+      for (int kk = 0; kk < KS; ++kk) {
+        const int k = 4 * kk + q;
+        const int kc = (k < K_) ? k : K_ - 1;
+        cfA[tm][kk] = Xs[m * K_ + kc];
+      }
+    }
+#pragma unroll
+    for (int tk = 0; tk < KT; ++tk) {
+      const int k = tk * 16 + r;
+      const int kc = (k < K_) ? k : K_ - 1;
+#pragma unroll
+      for (int ii = 0; ii < BS; ++ii) cbB[tk][ii] = Xs[(4 * ii + q) * K_ + kc];
+    }
+#pragma unroll
+    for (int tm = 0; tm < MT; ++tm)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) ctR[tm][i] = Ts[tm * 16 + q * 4 + i];
+  };
+
+  prefetch(0);
+  float loss_last = 0.f;
+  for (int s = 0; s < S; ++s) {
+    // batch the w reads (LDS; one unconditional read + select per kk)
+    float wv[KS];
+#pragma unroll
+    for (int kk = 0; kk < KS; ++kk) {
+      const int k = 4 * kk + q;
+      const float v = ws[(k < K_) ? k : K_ - 1];
+      wv[kk] = (r == 0 && k < K_) ? v : 0.f;
+    }
+    const float bterm = ws[32];
+
+    // ---- forward: y = X @ w + b ----
+    f32x4 acc[MT];
+#pragma unroll
+    for (int tm = 0; tm < MT; ++tm) acc[tm] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kk = 0; kk < KS; ++kk)
+#pragma unroll
+      for (int tm = 0; tm < MT; ++tm)
+        acc[tm] = __builtin_amdgcn_mfma_f32_16x16x4f32(cfA[tm][kk], wv[kk],
+                                                       acc[tm], 0, 0, 0);
+
+    // ---- loss grad (rows live on r==0 lanes) + dY exchange ----
+    // The squares are summed by one explicit fma per row: that is part of
+    // the loss word's bits (k_toy_multistep_chain reproduces it), and left
+    // to the compiler these unguarded rows become v_pk_mul + unfused adds
+    // (as in k_toy_multistep_bf16w, whose loss word is thus the compiler's
+    // choice and not bit-stable across compilers).
+    float loss_acc = 0.f;
+    if (r == 0) {
+#pragma unroll
+      for (int tm = 0; tm < MT; ++tm)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          float dy = 0.f;
+          if (use_mse) {
+            const float d = acc[tm][i] + bterm - ctR[tm][i];
+            loss_acc = __builtin_fmaf(d, d, loss_acc);
+            dy = d * inv2B;
+          }
+          dy_s[tm * 16 + q * 4 + i] = dy;
+        }
+    }
+    __syncthreads();  // dy_s visible to all lanes
+
+    // ---- backward: dw_k = sum_i dY_i X[i,k] ----
+    float av[BS];
+#pragma unroll
+    for (int ii = 0; ii < BS; ++ii) {
+      const float v = dy_s[4 * ii + q];  // unconditional read + select, as wv
+      av[ii] = (r == 0) ? v : 0.f;
+    }
+    f32x4 gacc[KT];
+#pragma unroll
+    for (int tk = 0; tk < KT; ++tk) gacc[tk] = {0.f, 0.f, 0.f, 0.f};
+    // db rides output column K_ of the bwd tile against a constant-1
+    // B-operand (K_ % 16 != 0 guarantees the free column) — same MFMA
+    // chain order as the single-step kernel, so history stays bitwise.
+    static_assert(K_ % 16 != 0, "free db column requires K_ % 16 != 0");
+#pragma unroll
+    for (int ii = 0; ii < BS; ++ii)
+#pragma unroll
+      for (int tk = 0; tk < KT; ++tk) {
+        const int k = tk * 16 + r;
+        const float bop = (k == K_) ? 1.f : cbB[tk][ii];
+        gacc[tk] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[ii], bop,
+                                                        gacc[tk], 0, 0, 0);
+      }
+
+    // cur regs are dead from here: load next step's operands straight into
+    // them — the vmcnt wait attaches to their first use (next iteration's
+    // forward MFMA), shadowed by the update/barrier below
+    if (s + 1 < S) prefetch(s + 1);
+
+    if (use_mse && loss_out && s == S - 1) loss_last = wave_sum(loss_acc);
+
+    if constexpr (MESH) {
+      float gval[KT];
+#pragma unroll
+      for (int tk = 0; tk < KT; ++tk) gval[tk] = gacc[tk][0];
+      const MeshArgs m{peer_slots, my_mb, mworld, minv_world, seq0, mesh_err};
+      if (!mesh_exchange<KT>(gval, K_, lane, r, q, m, s)) {
+        if (lane == 0) *mesh_err = 1u;
+        return;
+      }
+#pragma unroll
+      for (int tk = 0; tk < KT; ++tk) gacc[tk][0] = gval[tk];
+    }
+
+    // no barrier needed here: the dy_s barrier above already ordered this
+    // step's ws READS (forward) before these writes
+#pragma unroll
+    for (int tk = 0; tk < KT; ++tk) {
+      const int k = tk * 16 + r;
+      if (q == 0 && k < K_) {
+        wreg[tk] = wreg[tk] - lr * gacc[tk][0];
+        ws[k] = wreg[tk];
+      } else if (q == 0 && k == K_) {
+        ws[32] = bterm - lr * gacc[tk][0];
+      }
+    }
+    __syncthreads();  // ws update visible before next iteration's forward
+  }
+
+  if (lane < K_) param[w_off + lane] = ws[lane];
+  if (lane == K_) param[b_off] = ws[32];
+  if (lane == 0 && loss_out) *loss_out = use_mse ? loss_last / (float)B_ : 0.f;
 }
 
 // ---------------------------------------------------------------------------
@@ -400,11 +598,10 @@ k_toy_multistep_bf16w(const __hip_bfloat16* __restrict__ X,
                       __hip_bfloat16* __restrict__ param,
                       float* __restrict__ loss_out,
                       int S, int use_mse, int w_off, int b_off, float lr,
-                      MeshSlot* const* __restrict__ peer_slots = nullptr,
-                      MeshSlot* __restrict__ my_mb = nullptr,
-                      int mworld = 1, float minv_world = 1.f,
-                      unsigned long long seq0 = 0,
-                      unsigned int* __restrict__ mesh_err = nullptr) {
+                      MeshSlot* const* __restrict__ peer_slots,
+                      MeshSlot* __restrict__ my_mb, int mworld,
+                      float minv_world, unsigned long long seq0,
+                      unsigned int* __restrict__ mesh_err) {
   static_assert((B_ == 32 || B_ == 64) && K_ <= 32,
                 "bf16 wide path: B in {32, 64}, K<=32");
   constexpr int MT = B_ / 16;          // fwd 16-row tiles
@@ -554,9 +751,8 @@ k_toy_multistep_bf16w(const __hip_bfloat16* __restrict__ X,
       float gval[KT];
 #pragma unroll
       for (int tk = 0; tk < KT; ++tk) gval[tk] = gacc[tk][0];
-      if (!mesh_exchange<KT>(gval, K_, lane, r, q, peer_slots, my_mb,
-                             mworld, minv_world,
-                             seq0 + (unsigned long long)s)) {
+      const MeshArgs m{peer_slots, my_mb, mworld, minv_world, seq0, mesh_err};
+      if (!mesh_exchange<KT>(gval, K_, lane, r, q, m, s)) {
         if (lane == 0) *mesh_err = 1u;
         return false;
       }
@@ -584,196 +780,6 @@ k_toy_multistep_bf16w(const __hip_bfloat16* __restrict__ X,
     if (!body(setB, s + 1)) return;
   }
   if (s < S && !body(setA, s)) return;
-
-  if (lane < K_) stf(&param[w_off + lane], ws[lane]);
-  if (lane == K_) stf(&param[b_off], ws[32]);
-  if (lane == 0 && loss_out) *loss_out = use_mse ? loss_last / (float)B_ : 0.f;
-}
-
-template <typename T, int B_, int K_, bool MESH = false>
-__global__ void __launch_bounds__(64, 1)
-k_toy_multistep_spec(const T* __restrict__ X, const T* __restrict__ Tg,
-                     T* __restrict__ param, float* __restrict__ loss_out,
-                     int S, int use_mse, int w_off, int b_off, float lr,
-                     MeshSlot* const* __restrict__ peer_slots = nullptr,
-                     MeshSlot* __restrict__ my_mb = nullptr,
-                     int mworld = 1, float minv_world = 1.f,
-                     unsigned long long seq0 = 0,
-                     unsigned int* __restrict__ mesh_err = nullptr) {
-  constexpr int MT = (B_ + 15) / 16;   // fwd 16-row tiles
-  constexpr int KT = (K_ + 15) / 16;   // bwd 16-col tiles
-  constexpr int KS = (K_ + 3) / 4;     // fwd k-steps
-  constexpr int BS = (B_ + 3) / 4;     // bwd i-steps
-  const int lane = threadIdx.x;
-  const int r = lane & 15, q = lane >> 4;
-  __shared__ float ws[33];             // w (K_) + bias at ws[32]
-  __shared__ float dy_s[MT * 16];
-
-  if (lane < K_) ws[lane] = ldf(&param[w_off + lane]);
-  if (lane == K_) ws[32] = ldf(&param[b_off]);
-  const float inv2B = 2.f / (float)B_;
-  // updater lanes (q==0) also keep their w values in registers so the
-  // end-of-iteration update is WRITE-only to LDS (no dependent LDS read
-  // on the critical path); readers still take w from LDS
-  float wreg[KT];
-#pragma unroll
-  for (int tk = 0; tk < KT; ++tk) {
-    const int k = tk * 16 + r;
-    wreg[tk] = (k < K_) ? ldf(&param[w_off + ((k < K_) ? k : 0)]) : 0.f;
-  }
-
-  // Per-lane operand registers, software-pipelined: `c*` hold the step
-  // being computed, `n*` receive the next step's loads (issued at the top
-  // of the iteration, consumed — behind one vmcnt wait — at its end).
-  // All loads are UNCONDITIONAL with clamped addresses + value selects:
-  // ternary-guarded loads compile to exec-masked branch-per-element code
-  // that serializes the burst (seen in the r01b ISA), selects do not.
-  float cfA[MT][KS];  // fwd A: X[tm*16+r][4*kk+q]
-  float cbB[KT][BS];  // bwd B: X[4*ii+q][tk*16+r]
-  float ctR[MT][4];   // targets for rows tm*16+q*4+i
-
-  auto prefetch = [&](int s) {
-    const T* Xs = X + (size_t)s * (B_ * K_);
-    const T* Ts = Tg + (size_t)s * B_;
-    // Loads are raw (address-clamped, no value select): out-of-range
-    // lanes load in-bounds garbage whose products are either multiplied
-    // by a zeroed LDS-side operand (wv/av) or discarded by the guarded
-    // ws/dy writes — so no per-load mask, and therefore no vmcnt wait
-    // until the next iteration's first MFMA use.
-#pragma unroll
-    for (int tm = 0; tm < MT; ++tm) {
-      const int m = tm * 16 + r;
-      const int mc = (m < B_) ? m : B_ - 1;
-#pragma unroll
-      for (int kk = 0; kk < KS; ++kk) {
-        const int k = 4 * kk + q;
-        const int kc = (k < K_) ? k : K_ - 1;
-        cfA[tm][kk] = ldf(&Xs[mc * K_ + kc]);
-      }
-    }
-#pragma unroll
-    for (int tk = 0; tk < KT; ++tk) {
-      const int k = tk * 16 + r;
-      const int kc = (k < K_) ? k : K_ - 1;
-#pragma unroll
-      for (int ii = 0; ii < BS; ++ii) {
-        const int i = 4 * ii + q;
-        const int ic = (i < B_) ? i : B_ - 1;
-        cbB[tk][ii] = ldf(&Xs[ic * K_ + kc]);
-      }
-    }
-#pragma unroll
-    for (int tm = 0; tm < MT; ++tm)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int row = tm * 16 + q * 4 + i;
-        ctR[tm][i] = ldf(&Ts[(row < B_) ? row : B_ - 1]);
-      }
-  };
-
-  prefetch(0);
-  float loss_last = 0.f;
-  for (int s = 0; s < S; ++s) {
-    // batch the w reads (LDS; one unconditional read + select per kk)
-    float wv[KS];
-#pragma unroll
-    for (int kk = 0; kk < KS; ++kk) {
-      const int k = 4 * kk + q;
-      const float v = ws[(k < K_) ? k : K_ - 1];
-      wv[kk] = (r == 0 && k < K_) ? v : 0.f;
-    }
-    const float bterm = ws[32];
-
-    // ---- forward: y = X @ w + b ----
-    f32x4 acc[MT];
-#pragma unroll
-    for (int tm = 0; tm < MT; ++tm) acc[tm] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kk = 0; kk < KS; ++kk)
-#pragma unroll
-      for (int tm = 0; tm < MT; ++tm)
-        acc[tm] = __builtin_amdgcn_mfma_f32_16x16x4f32(cfA[tm][kk], wv[kk],
-                                                       acc[tm], 0, 0, 0);
-
-    // ---- loss grad (rows live on r==0 lanes) + dY exchange ----
-    float loss_acc = 0.f;
-    if (r == 0) {
-#pragma unroll
-      for (int tm = 0; tm < MT; ++tm)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int row = tm * 16 + q * 4 + i;
-          float dy = 0.f;
-          if (row < B_ && use_mse) {
-            const float d = acc[tm][i] + bterm - ctR[tm][i];
-            loss_acc += d * d;
-            dy = d * inv2B;
-          }
-          if (row < B_) dy_s[row] = dy;
-        }
-    }
-    __syncthreads();  // dy_s visible to all lanes
-
-    // ---- backward: dw_k = sum_i dY_i X[i,k] ----
-    float av[BS];
-#pragma unroll
-    for (int ii = 0; ii < BS; ++ii) {
-      const int i = 4 * ii + q;
-      const float v = dy_s[(i < B_) ? i : B_ - 1];
-      av[ii] = (r == 0 && i < B_) ? v : 0.f;
-    }
-    f32x4 gacc[KT];
-#pragma unroll
-    for (int tk = 0; tk < KT; ++tk) gacc[tk] = {0.f, 0.f, 0.f, 0.f};
-    // db rides output column K_ of the bwd tile against a constant-1
-    // B-operand (K_ % 16 != 0 guarantees the free column) — same MFMA
-    // chain order as the single-step kernel, so history stays bitwise.
-    static_assert(K_ % 16 != 0, "free db column requires K_ % 16 != 0");
-#pragma unroll
-    for (int ii = 0; ii < BS; ++ii)
-#pragma unroll
-      for (int tk = 0; tk < KT; ++tk) {
-        const int k = tk * 16 + r;
-        const float bop = (k == K_) ? 1.f : cbB[tk][ii];
-        gacc[tk] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[ii], bop,
-                                                        gacc[tk], 0, 0, 0);
-      }
-
-    // cur regs are dead from here: load next step's operands straight into
-    // them — the vmcnt wait attaches to their first use (next iteration's
-    // forward MFMA), shadowed by the update/barrier below
-    if (s + 1 < S) prefetch(s + 1);
-
-    if (use_mse && loss_out && s == S - 1) loss_last = wave_sum(loss_acc);
-
-    if constexpr (MESH) {
-      float gval[KT];
-#pragma unroll
-      for (int tk = 0; tk < KT; ++tk) gval[tk] = gacc[tk][0];
-      if (!mesh_exchange<KT>(gval, K_, lane, r, q, peer_slots, my_mb,
-                             mworld, minv_world,
-                             seq0 + (unsigned long long)s)) {
-        if (lane == 0) *mesh_err = 1u;
-        return;
-      }
-#pragma unroll
-      for (int tk = 0; tk < KT; ++tk) gacc[tk][0] = gval[tk];
-    }
-
-    // no barrier needed here: the dy_s barrier above already ordered this
-    // step's ws READS (forward) before these writes
-#pragma unroll
-    for (int tk = 0; tk < KT; ++tk) {
-      const int k = tk * 16 + r;
-      if (q == 0 && k < K_) {
-        wreg[tk] = round_store<T>(wreg[tk] - lr * gacc[tk][0]);
-        ws[k] = wreg[tk];
-      } else if (q == 0 && k == K_) {
-        ws[32] = round_store<T>(bterm - lr * gacc[tk][0]);
-      }
-    }
-    __syncthreads();  // ws update visible before next iteration's forward
-  }
 
   if (lane < K_) stf(&param[w_off + lane], ws[lane]);
   if (lane == K_) stf(&param[b_off], ws[32]);
@@ -1246,16 +1252,6 @@ static void with_fast_batch(int B, F&& fn) {
   else fn(std::integral_constant<int, 64>{});
 }
 
-// Mesh arguments of the fast MFMA kernels; the defaults are the no-mesh call.
-struct MeshArgs {
-  MeshSlot* const* peer_slots = nullptr;
-  MeshSlot* my_mb = nullptr;
-  int world = 1;
-  float inv_world = 1.f;
-  unsigned long long seq0 = 0;
-  unsigned int* err = nullptr;
-};
-
 // The fast MFMA multi-step kernels (batch 32/64, K 20): native bf16 MFMA
 // (16x16x32, whole contraction in one MFMA per tile; the batch-64 backward
 // as two chained chunks) for bf16 storage, the f32 spec kernel otherwise.
@@ -1268,7 +1264,7 @@ static void launch_toy_multistep_mfma(const T* xp, const T* tp, T* pp,
     if constexpr (std::is_same<T, __hip_bfloat16>::value)
       return &k_toy_multistep_bf16w<B_, 20, MESH>;
     else
-      return &k_toy_multistep_spec<T, B_, 20, MESH>;
+      return &k_toy_multistep_spec<B_, 20, MESH>;
   }();
   hipLaunchKernelGGL(kptr, dim3(1), dim3(64), 0, cur_stream(), xp, tp, pp,
                      lossp, S, use_mse ? 1 : 0, w_off, b_off, lr, m.peer_slots,

@@ -338,7 +338,7 @@ def test_persistent_deferral_state_machine_fuzz():
 
 
 def test_spec_multistep_batch64_bitwise():
-    # the batch-64 instantiation of the fast-path kernel (246 VGPRs, no
+    # the batch-64 instantiation of the fast-path kernel (no register
     # spills) == repeated single-step launches, bitwise
     from mi355x_ddp.engine import PersistentToyStep, ToyFusedStep
     from mi355x_ddp.models import toy_model
@@ -408,3 +408,42 @@ def test_bf16_multistep_batch64():
     assert torch.allclose(w_multi, w_ref, atol=5e-3, rtol=5e-2), \
         (w_multi - w_ref).abs().max()
     assert torch.allclose(b_multi, b_ref, atol=5e-3, rtol=5e-2)
+
+
+@pytest.mark.parametrize("S", [1, 2, 3, 5])
+@pytest.mark.parametrize("B", [32, 64])
+def test_bf16_multistep_launch_split_bitwise(B, S):
+    # the bf16 wide kernel runs even steps through one operand register set,
+    # odd steps through the other and a tail through the first: one launch
+    # of S steps == S launches of one step, bitwise, params and loss word
+    from mi355x_ddp import ops
+    from mi355x_ddp.models import toy_model
+    from mi355x_ddp.parallel.reducer import Reducer
+
+    g = torch.Generator().manual_seed(31)
+    X = torch.rand(S * B, 20, generator=g).to(DEV).bfloat16()
+    T = torch.rand(S * B, 1, generator=g).to(DEV).bfloat16()
+
+    def run(steps_per_launch):
+        torch.manual_seed(8)
+        m = toy_model(20, 1).to(DEV).bfloat16()
+        red = Reducer(list(m.parameters()), comm=None)
+        b = red.buckets[0]
+        w_off = b.offsets[red._param_index[m.weight][1]]
+        b_off = b.offsets[red._param_index[m.bias][1]]
+        p0 = b.flat_param.clone()
+        loss = torch.full((1,), -1.0, device=DEV)
+        n = steps_per_launch * B
+        for lo in range(0, S * B, n):
+            ops.ext().toy_multistep(X[lo:lo + n], T[lo:lo + n], b.flat_param,
+                                    loss, True, w_off, b_off, 0.04, B)
+        torch.cuda.synchronize()
+        assert not torch.equal(b.flat_param, p0)  # the steps moved the params
+        return b.flat_param.clone(), loss.clone()
+
+    p_one, loss_one = run(S)
+    p_split, loss_split = run(1)
+    assert torch.equal(p_one, p_split), \
+        (p_one.float() - p_split.float()).abs().max()
+    assert torch.equal(loss_one, loss_split), (loss_one, loss_split)
+    assert loss_one.item() > 0.0
