@@ -5,9 +5,10 @@
 // Re-implements the native components the reference pulls in implicitly
 // (SURVEY.md §2.2): N6 GEMM fwd/bwd for the toy Linear (reference
 // single_gpu.py:23,25 / nn.Linear(20,1) at :50), N7 CE/MSE loss kernels
-// (single_gpu.py:24, multinode_torchrun.py:46), N8 fused SGD
-// (single_gpu.py:26), N9 zero_grad folded into the bucket lifecycle
-// (single_gpu.py:22), and the reducer's bucket flatten/unflatten (N3).
+// (single_gpu.py:24, multinode_torchrun.py:46), N9 zero_grad folded into
+// the bucket lifecycle (single_gpu.py:22), and the reducer's bucket
+// flatten/unflatten (N3). N8, the fused SGD (single_gpu.py:26), is in
+// optim_kernels.hip with the other flat-bucket optimizers.
 //
 // Dtypes: every kernel is templated on the STORAGE type (f32 or bf16;
 // bf16 is the BASELINE.json config-2 capability). Matmul compute uses
@@ -17,12 +18,12 @@
 // and latency-bound, so the MFMA path buys kernel-count and issue-slot
 // economy, not FLOPs.
 //
-// This file holds the general-purpose kernels: linear fwd/bwd, the bf16
-// GEMM, CE/MSE, fused SGD, the bucket copy, and the epoch shard gather —
-// `k_epoch_shard` fuses the epoch shuffle into one copy pass, and
-// `k_epoch_shard_multi` gathers a whole BLOCK of epochs per launch so
-// the engine's deferral spans epoch boundaries (profiles r01q). The fused
-// toy training-step family lives in toy_kernels.hip.
+// This file holds the general-purpose kernels: the linear tile kernel
+// `k_linear_tile` (forward and dX, serial and split), `k_linear_bwd_w`, the
+// bf16 GEMM `k_gemm_bf16`, CE/MSE (`k_ce_*`, `k_mse_*`), the bucket copy
+// `k_bucket_copy`, and the epoch shard gather `k_epoch_shard_multi`, which
+// fuses the epoch shuffle into one copy pass over a whole BLOCK of epochs.
+// The fused toy training-step family lives in toy_kernels.hip.
 
 #include <hip/hip_runtime.h>
 
@@ -35,123 +36,117 @@
 namespace mi355x {
 
 // ---------------------------------------------------------------------------
-// Linear forward: Y[B,N] = X[B,K] @ W[N,K]^T + bias[N]
+// Linear tile kernel: C[M,Nc] = A[M,Kc] @ Bop[Kc,Nc].
+//   forward (B_T):  Y = X @ W^T + b, Bop[k][n] = W[n*Kc + k], W is [Nc,Kc]
+//   dX     (!B_T):  dX = dY @ W,     Bop[k][n] = W[k*Nc + n], W is [Kc,Nc]
+// Only the forward adds a bias (bias may be null); dX ignores the argument
+// and stores the accumulator as it is — adding a run-time zero instead cost
+// the serial dX 0.4% (profiles r05a).
 // One wave (64 lanes) per 16x16 output tile; K-loop of mfma_f32_16x16x4f32
 // (storage loads upconvert bf16 -> f32; exact-f32 accumulate).
 // Lane maps (cdna_hip_programming.md §3): A[l&15][k=l>>4], B[k=l>>4][l&15],
 // C/D col=lane&15, row=(lane>>4)*4+reg.
+// !SPLIT: the 4 waves of a workgroup take 4 consecutive M-tiles.
+// SPLIT, for small-M / long-contraction shapes (e.g. the ResNet-50 FC,
+// 32x2048 @ 2048x1000, and its dX): the 4 waves contract DISJOINT slices of
+// the SAME output tile and reduce partials through LDS — 4x the
+// memory-level parallelism on shapes where M-tiling cannot fill the chip.
 // ---------------------------------------------------------------------------
-template <typename T>
-__global__ void k_linear_fwd(const T* __restrict__ X, const T* __restrict__ W,
-                             const T* __restrict__ bias, T* __restrict__ Y,
-                             int B, int K, int N) {
+template <typename T, bool B_T, bool SPLIT>
+__global__ void k_linear_tile(const T* __restrict__ A, const T* __restrict__ W,
+                              const T* __restrict__ bias, T* __restrict__ C,
+                              int M, int Kc, int Nc) {
   const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;  // 4 waves/block, each one M-tile
-  const int tile_m = blockIdx.x * 4 + wave;
+  const int wave = threadIdx.x >> 6;
+  const int tile_m = SPLIT ? blockIdx.x : blockIdx.x * 4 + wave;
   const int tile_n = blockIdx.y;
-  if (tile_m * 16 >= B) return;
+  if (!SPLIT && tile_m * 16 >= M) return;
   const int r = lane & 15;
   const int q = lane >> 4;
-  const int m = tile_m * 16 + r;   // A row for this lane
-  const int n = tile_n * 16 + r;   // B column (j) for this lane
+  const int m = tile_m * 16 + r;  // A row for this lane
+  const int n = tile_n * 16 + r;  // Bop column for this lane
+  int k_lo = 0, k_hi = Kc;
+  if constexpr (SPLIT) {
+    const int kq = (((Kc + 3) / 4 + 3) / 4) * 4;  // slice per wave (mult of 4)
+    k_lo = wave * kq;
+    k_hi = min(Kc, (wave + 1) * kq);
+  }
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  for (int k0 = 0; k0 < K; k0 += 4) {
+  for (int k0 = k_lo; k0 < k_hi; k0 += 4) {
     const int k = k0 + q;
-    const float a = (m < B && k < K) ? ldf(&X[(size_t)m * K + k]) : 0.f;
-    const float b = (n < N && k < K) ? ldf(&W[(size_t)n * K + k]) : 0.f;
+    const float a = (m < M && k < Kc) ? ldf(&A[(size_t)m * Kc + k]) : 0.f;
+    const size_t wi = B_T ? (size_t)n * Kc + k : (size_t)k * Nc + n;
+    const float b = (n < Nc && k < Kc) ? ldf(&W[wi]) : 0.f;
     acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
   }
   const int col = tile_n * 16 + r;
-  if (col < N) {
-    const float bv = bias ? ldf(&bias[col]) : 0.f;
+  if constexpr (SPLIT) {
+    __shared__ float red[4][64][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) red[wave][lane][i] = acc[i];
+    __syncthreads();
+    if (wave == 0) {
+      const float bv = (B_T && bias && col < Nc) ? ldf(&bias[col]) : 0.f;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int row = tile_m * 16 + q * 4 + i;
+        if (row < M && col < Nc) {
+          const float v = red[0][lane][i] + red[1][lane][i] +
+                          red[2][lane][i] + red[3][lane][i];
+          stf(&C[(size_t)row * Nc + col], B_T ? v + bv : v);
+        }
+      }
+    }
+  } else if (col < Nc) {
+    const float bv = (B_T && bias) ? ldf(&bias[col]) : 0.f;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int row = tile_m * 16 + q * 4 + i;
-      if (row < B) stf(&Y[(size_t)row * N + col], acc[i] + bv);
+      if (row < M)
+        stf(&C[(size_t)row * Nc + col], B_T ? acc[i] + bv : acc[i]);
     }
   }
 }
 
-// Split-K variant for small-M / large-K shapes (e.g. the ResNet-50 FC,
-// 32x2048 @ 2048x1000): the 4 waves of a workgroup contract DISJOINT
-// K-slices of the SAME 16x16 output tile and reduce partials through LDS —
-// 4x the memory-level parallelism of the serial-K kernel on shapes where
-// M-tiling alone cannot fill the chip.
-template <typename T>
-__global__ void k_linear_fwd_splitk(const T* __restrict__ X,
-                                    const T* __restrict__ W,
-                                    const T* __restrict__ bias,
-                                    T* __restrict__ Y, int B, int K, int N) {
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int tile_m = blockIdx.x;
-  const int tile_n = blockIdx.y;
-  const int r = lane & 15;
-  const int q = lane >> 4;
-  const int m = tile_m * 16 + r;
-  const int n = tile_n * 16 + r;
-  const int kq = (((K + 3) / 4 + 3) / 4) * 4;  // K-slice per wave (mult of 4)
-  const int k_lo = wave * kq, k_hi = min(K, (wave + 1) * kq);
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-  for (int k0 = k_lo; k0 < k_hi; k0 += 4) {
-    const int k = k0 + q;
-    const float a = (m < B && k < K) ? ldf(&X[(size_t)m * K + k]) : 0.f;
-    const float b = (n < N && k < K) ? ldf(&W[(size_t)n * K + k]) : 0.f;
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
-  }
-  __shared__ float red[4][64][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) red[wave][lane][i] = acc[i];
-  __syncthreads();
-  if (wave == 0) {
-    const int col = tile_n * 16 + r;
-    const float bv = (bias && col < N) ? ldf(&bias[col]) : 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = tile_m * 16 + q * 4 + i;
-      if (row < B && col < N) {
-        const float v = red[0][lane][i] + red[1][lane][i] +
-                        red[2][lane][i] + red[3][lane][i];
-        stf(&Y[(size_t)row * N + col], v + bv);
-      }
-    }
-  }
+// Picks the split form for M < 64, the serial one otherwise.
+template <bool B_T>
+static torch::Tensor linear_tile(const torch::Tensor& a, const torch::Tensor& w,
+                                 const c10::optional<torch::Tensor>& bias,
+                                 const char* name) {
+  TORCH_CHECK(a.is_cuda() && w.is_cuda(), name, ": operands must be on device");
+  TORCH_CHECK(a.dim() == 2 && w.dim() == 2 &&
+                  a.size(1) == w.size(B_T ? 1 : 0),
+              name, ": shape mismatch");
+  TORCH_CHECK(a.scalar_type() == w.scalar_type(), name, ": dtype mismatch");
+  auto ac = a.contiguous();
+  auto wc = w.contiguous();
+  const int M = (int)ac.size(0), Kc = (int)ac.size(1);
+  const int Nc = (int)wc.size(B_T ? 0 : 1);
+  auto c = at::empty({M, Nc}, a.options());
+  torch::Tensor bc;
+  if (bias.has_value()) bc = bias->contiguous();
+  const bool split = M < 64;
+  const dim3 grid(cdiv(M, split ? 16 : 64), cdiv(Nc, 16));
+  DISPATCH_F32_BF16(a.scalar_type(), name, {
+    auto kernel = split ? k_linear_tile<scalar_t, B_T, true>
+                        : k_linear_tile<scalar_t, B_T, false>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, cur_stream(),
+                       cdptr<scalar_t>(ac), cdptr<scalar_t>(wc),
+                       bc.defined() ? cdptr<scalar_t>(bc) : nullptr,
+                       dptr<scalar_t>(c), M, Kc, Nc);
+  });
+  HIP_OK(hipGetLastError());
+  return c;
 }
 
 torch::Tensor linear_fwd(torch::Tensor x, torch::Tensor w,
                          c10::optional<torch::Tensor> bias) {
-  TORCH_CHECK(x.is_cuda(), "x must be on device");
-  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.size(1) == w.size(1),
-              "shape mismatch for linear");
-  TORCH_CHECK(x.scalar_type() == w.scalar_type(), "x/w dtype mismatch");
-  auto xc = x.contiguous();
-  auto wc = w.contiguous();
-  const int B = (int)xc.size(0), K = (int)xc.size(1), N = (int)wc.size(0);
-  auto y = at::empty({B, N}, x.options());
-  torch::Tensor bc;
-  bool has_bias = bias.has_value();
-  if (has_bias) bc = bias->contiguous();
-  if (B < 64) {  // small-M: split the contraction across the block's waves
-    dim3 grid(cdiv(B, 16), cdiv(N, 16));
-    DISPATCH_F32_BF16(x.scalar_type(), "linear_fwd", {
-      hipLaunchKernelGGL((k_linear_fwd_splitk<scalar_t>), grid, dim3(256), 0,
-                         cur_stream(), cdptr<scalar_t>(xc), cdptr<scalar_t>(wc),
-                         has_bias ? cdptr<scalar_t>(bc) : nullptr,
-                         dptr<scalar_t>(y), B, K, N);
-    });
-    HIP_OK(hipGetLastError());
-    return y;
-  }
-  dim3 grid(cdiv(B, 64), cdiv(N, 16));
-  DISPATCH_F32_BF16(x.scalar_type(), "linear_fwd", {
-    hipLaunchKernelGGL((k_linear_fwd<scalar_t>), grid, dim3(256), 0,
-                       cur_stream(), cdptr<scalar_t>(xc), cdptr<scalar_t>(wc),
-                       has_bias ? cdptr<scalar_t>(bc) : nullptr,
-                       dptr<scalar_t>(y), B, K, N);
-  });
-  HIP_OK(hipGetLastError());
-  return y;
+  return linear_tile<true>(x, w, bias, "linear_fwd");
+}
+
+// dX[B,K] = dY[B,N] @ W[N,K]
+torch::Tensor linear_bwd_input(torch::Tensor dy, torch::Tensor w) {
+  return linear_tile<false>(dy, w, c10::nullopt, "linear_bwd_input");
 }
 
 // ---------------------------------------------------------------------------
@@ -193,11 +188,6 @@ __global__ void k_linear_bwd_w(const T* __restrict__ X,
         }
       }
     }
-  } else if (tile_k == 0) {
-    for (int i0 = 0; i0 < B; i0 += 4) {
-      const int i = i0 + q;
-      bsum += (i < B && j < N) ? ldf(&dY[(size_t)i * N + j]) : 0.f;
-    }
   }
   if (tile_k == 0 && dB) {
     // combine the four q-chunks of lane-row r: lanes r, r+16, r+32, r+48
@@ -226,112 +216,15 @@ void linear_bwd_weight(torch::Tensor x, torch::Tensor dy,
   HIP_OK(hipGetLastError());
 }
 
-// dX[B,K] = dY[B,N] @ W[N,K]
-template <typename T>
-__global__ void k_linear_bwd_x(const T* __restrict__ dY,
-                               const T* __restrict__ W, T* __restrict__ dX,
-                               int B, int K, int N) {
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int tile_m = blockIdx.x * 4 + wave;
-  const int tile_k = blockIdx.y;
-  if (tile_m * 16 >= B) return;
-  const int r = lane & 15;
-  const int q = lane >> 4;
-  const int m = tile_m * 16 + r;   // dY row
-  const int kc = tile_k * 16 + r;  // W column for B operand
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  for (int j0 = 0; j0 < N; j0 += 4) {
-    const int j = j0 + q;
-    const float a = (m < B && j < N) ? ldf(&dY[(size_t)m * N + j]) : 0.f;
-    const float b = (j < N && kc < K) ? ldf(&W[(size_t)j * K + kc]) : 0.f;
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
-  }
-  const int col = tile_k * 16 + r;
-  if (col < K) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = tile_m * 16 + q * 4 + i;
-      if (row < B) stf(&dX[(size_t)row * K + col], acc[i]);
-    }
-  }
-}
-
-// Split-N variant of dX (same rationale as k_linear_fwd_splitk: the
-// contraction over N=1000+ is split across the block's 4 waves).
-template <typename T>
-__global__ void k_linear_bwd_x_splitk(const T* __restrict__ dY,
-                                      const T* __restrict__ W,
-                                      T* __restrict__ dX, int B, int K, int N) {
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int tile_m = blockIdx.x;
-  const int tile_k = blockIdx.y;
-  const int r = lane & 15;
-  const int q = lane >> 4;
-  const int m = tile_m * 16 + r;
-  const int kc = tile_k * 16 + r;
-  const int nq = (((N + 3) / 4 + 3) / 4) * 4;
-  const int j_lo = wave * nq, j_hi = min(N, (wave + 1) * nq);
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-  for (int j0 = j_lo; j0 < j_hi; j0 += 4) {
-    const int j = j0 + q;
-    const float a = (m < B && j < N) ? ldf(&dY[(size_t)m * N + j]) : 0.f;
-    const float b = (j < N && kc < K) ? ldf(&W[(size_t)j * K + kc]) : 0.f;
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
-  }
-  __shared__ float red[4][64][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) red[wave][lane][i] = acc[i];
-  __syncthreads();
-  if (wave == 0) {
-    const int col = tile_k * 16 + r;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = tile_m * 16 + q * 4 + i;
-      if (row < B && col < K) {
-        stf(&dX[(size_t)row * K + col],
-            red[0][lane][i] + red[1][lane][i] +
-            red[2][lane][i] + red[3][lane][i]);
-      }
-    }
-  }
-}
-
-torch::Tensor linear_bwd_input(torch::Tensor dy, torch::Tensor w) {
-  auto dyc = dy.contiguous();
-  auto wc = w.contiguous();
-  const int B = (int)dyc.size(0), N = (int)dyc.size(1), K = (int)wc.size(1);
-  auto dx = at::empty({B, K}, dy.options());
-  if (B < 64) {
-    dim3 grid(cdiv(B, 16), cdiv(K, 16));
-    DISPATCH_F32_BF16(dy.scalar_type(), "linear_bwd_input", {
-      hipLaunchKernelGGL((k_linear_bwd_x_splitk<scalar_t>), grid, dim3(256), 0,
-                         cur_stream(), cdptr<scalar_t>(dyc), cdptr<scalar_t>(wc),
-                         dptr<scalar_t>(dx), B, K, N);
-    });
-    HIP_OK(hipGetLastError());
-    return dx;
-  }
-  dim3 grid(cdiv(B, 64), cdiv(K, 16));
-  DISPATCH_F32_BF16(dy.scalar_type(), "linear_bwd_input", {
-    hipLaunchKernelGGL((k_linear_bwd_x<scalar_t>), grid, dim3(256), 0,
-                       cur_stream(), cdptr<scalar_t>(dyc), cdptr<scalar_t>(wc),
-                       dptr<scalar_t>(dx), B, K, N);
-  });
-  HIP_OK(hipGetLastError());
-  return dx;
-}
-
 // ---------------------------------------------------------------------------
 // Standalone bf16 MFMA GEMM: Y[B,N] = X[B,K] @ W[N,K]^T (+bias), f32
 // accumulate via v_mfma_f32_16x16x32_bf16 (the gfx950 2xK form). One wave
 // per 16x16 tile, K consumed 32 at a time, 8 bf16 per lane per operand.
 // A: lane l holds A[l&15][(l>>4)*8 + j], j=0..7; B-op: W[l&15][(l>>4)*8+j];
 // C/D: col=lane&15, row=(lane>>4)*4+reg (cdna_hip_programming.md §3).
-// Used for larger HipLinear shapes in bf16 models; verified against torch
-// in tests/test_kernels_gpu.py.
+// No model path routes here (HipLinear takes k_linear_tile or rocBLAS); it
+// is bound as ops.ext().gemm_bf16, verified against torch in
+// tests/test_bf16_gpu.py and timed by tools/bench_kernels.py.
 // ---------------------------------------------------------------------------
 __global__ void k_gemm_bf16(const __hip_bfloat16* __restrict__ X,
                             const __hip_bfloat16* __restrict__ W,
@@ -452,6 +345,16 @@ std::vector<torch::Tensor> ce_fwd(torch::Tensor y, torch::Tensor t) {
   return {loss, probs, tsum};
 }
 
+// The optional incoming scalar grad of ce_bwd / mse_bwd, as a device pointer.
+static const float* gout_ptr(const c10::optional<torch::Tensor>& gout,
+                             const char* name) {
+  if (!gout.has_value()) return nullptr;
+  TORCH_CHECK(gout->is_cuda() && gout->numel() == 1 &&
+                  gout->scalar_type() == at::kFloat,
+              name, " gout must be a device f32 scalar");
+  return gout->data_ptr<float>();
+}
+
 // dY = (tsum_row * p - t) * grad_scale / B
 template <typename T>
 __global__ void k_ce_bwd(const float* __restrict__ P, const T* __restrict__ Tg,
@@ -476,13 +379,7 @@ torch::Tensor ce_bwd(torch::Tensor probs, torch::Tensor t,
   auto tc = t.contiguous();
   auto dy = at::empty({B, C}, tc.options());
   const int64_t n = (int64_t)B * C;
-  const float* gp = nullptr;
-  if (gout.has_value()) {
-    TORCH_CHECK(gout->is_cuda() && gout->numel() == 1 &&
-                gout->scalar_type() == at::kFloat,
-                "ce_bwd gout must be a device f32 scalar");
-    gp = gout->data_ptr<float>();
-  }
+  const float* gp = gout_ptr(gout, "ce_bwd");
   DISPATCH_F32_BF16(tc.scalar_type(), "ce_bwd", {
     hipLaunchKernelGGL((k_ce_bwd<scalar_t>), dim3(cdiv(n, 256)), dim3(256), 0,
                        cur_stream(), probs.data_ptr<float>(),
@@ -555,13 +452,7 @@ torch::Tensor mse_bwd(torch::Tensor y, torch::Tensor t, double grad_scale,
   auto tc = t.contiguous();
   const int64_t n = yc.numel();
   auto dy = at::empty_like(yc);
-  const float* gp = nullptr;
-  if (gout.has_value()) {
-    TORCH_CHECK(gout->is_cuda() && gout->numel() == 1 &&
-                gout->scalar_type() == at::kFloat,
-                "mse_bwd gout must be a device f32 scalar");
-    gp = gout->data_ptr<float>();
-  }
+  const float* gp = gout_ptr(gout, "mse_bwd");
   DISPATCH_F32_BF16(y.scalar_type(), "mse_bwd", {
     hipLaunchKernelGGL((k_mse_bwd<scalar_t>), dim3(cdiv(n, 256)), dim3(256), 0,
                        cur_stream(), cdptr<scalar_t>(yc), cdptr<scalar_t>(tc),
@@ -570,67 +461,6 @@ torch::Tensor mse_bwd(torch::Tensor y, torch::Tensor t, double grad_scale,
   });
   HIP_OK(hipGetLastError());
   return dy;
-}
-
-// ---------------------------------------------------------------------------
-// Fused SGD over a flat bucket (+ fold zero_grad): p -= lr * g; g = 0.
-// 4 elements per lane (16 B for f32, 8 B for bf16); bucket lengths are
-// padded to a multiple of 4 elements by the reducer.
-// ---------------------------------------------------------------------------
-__global__ void k_sgd_flat_f32(float4* __restrict__ p, float4* __restrict__ g,
-                               float lr, int64_t n4, int zero) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n4) return;
-  float4 gv = g[i];
-  float4 pv = p[i];
-  pv.x -= lr * gv.x; pv.y -= lr * gv.y; pv.z -= lr * gv.z; pv.w -= lr * gv.w;
-  p[i] = pv;
-  if (zero) g[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-}
-
-// bf16 variant: 4 elements = one 8-byte ushort4 per lane (vectorized load;
-// hipcc does not auto-vectorize scalar bf16 — guide G13)
-__global__ void k_sgd_flat_bf16(ushort4* __restrict__ p, ushort4* __restrict__ g,
-                                float lr, int64_t n4, int zero) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n4) return;
-  ushort4 gv = g[i];
-  ushort4 pv = p[i];
-  unsigned short* gs = &gv.x;
-  unsigned short* ps = &pv.x;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float pf = __bfloat162float(*reinterpret_cast<__hip_bfloat16*>(ps + j));
-    const float gf = __bfloat162float(*reinterpret_cast<__hip_bfloat16*>(gs + j));
-    const __hip_bfloat16 out = __float2bfloat16(pf - lr * gf);
-    ps[j] = *reinterpret_cast<const unsigned short*>(&out);
-  }
-  p[i] = pv;
-  if (zero) g[i] = make_ushort4(0, 0, 0, 0);
-}
-
-void sgd_flat(torch::Tensor param_flat, torch::Tensor grad_flat,
-              double lr, bool zero_grad) {
-  TORCH_CHECK(param_flat.is_cuda() && param_flat.is_contiguous() &&
-              grad_flat.is_contiguous(), "flat buffers must be contiguous");
-  TORCH_CHECK(param_flat.numel() % 4 == 0,
-              "bucket length must be padded to a multiple of 4");
-  const int64_t n4 = param_flat.numel() / 4;
-  const dim3 grid(cdiv(n4, 256));
-  if (param_flat.scalar_type() == at::kFloat) {
-    hipLaunchKernelGGL(k_sgd_flat_f32, grid, dim3(256), 0, cur_stream(),
-                       reinterpret_cast<float4*>(param_flat.data_ptr()),
-                       reinterpret_cast<float4*>(grad_flat.data_ptr()),
-                       (float)lr, n4, zero_grad ? 1 : 0);
-  } else if (param_flat.scalar_type() == at::kBFloat16) {
-    hipLaunchKernelGGL(k_sgd_flat_bf16, grid, dim3(256), 0, cur_stream(),
-                       reinterpret_cast<ushort4*>(param_flat.data_ptr()),
-                       reinterpret_cast<ushort4*>(grad_flat.data_ptr()),
-                       (float)lr, n4, zero_grad ? 1 : 0);
-  } else {
-    TORCH_CHECK(false, "sgd_flat: unsupported dtype");
-  }
-  HIP_OK(hipGetLastError());
 }
 
 // ---------------------------------------------------------------------------
@@ -712,8 +542,16 @@ void unflatten_from(torch::Tensor bucket, torch::Tensor plan, int64_t total_bloc
 // so one linear copy pass replaces torch.randperm's radix sort + two
 // index_select launches (~30 us -> ~3 us per epoch). Python mirror:
 // mi355x_ddp.ops.perm_index (tested for permutation property + parity).
+//
+// One launch gathers `epochs` consecutive epoch shards (seeds seed0,
+// seed0+1, …) into one contiguous buffer pair; block e is what a
+// single-epoch launch with seed0+e writes. This is what lets the
+// persistent-engine deferral span epoch boundaries (one multistep launch
+// per ~max_defer steps instead of one per epoch, profiles r01q) and, as a
+// side effect, gives this gather kernel epochs× more workgroups to fill the
+// 256 CUs with.
 // ---------------------------------------------------------------------------
-__device__ __host__ __forceinline__ uint32_t mix_bijection(
+__device__ __forceinline__ uint32_t mix_bijection(
     uint32_t x, uint32_t k_mask, uint32_t n, uint32_t c0, uint32_t m0,
     uint32_t c1, uint32_t m1) {
   // each op is bijective on (k_mask+1)-space; cycle-walk back into [0, n)
@@ -728,7 +566,7 @@ __device__ __host__ __forceinline__ uint32_t mix_bijection(
   return x;
 }
 
-__device__ __host__ __forceinline__ void shard_consts(
+__device__ __forceinline__ void shard_consts(
     uint32_t seed, uint32_t* c0, uint32_t* m0, uint32_t* c1, uint32_t* m1) {
   uint32_t z = seed * 0x9E3779B9u + 0x7F4A7C15u;
   z ^= z >> 15; z *= 0x2C1B3C6Du; z ^= z >> 12;
@@ -739,55 +577,6 @@ __device__ __host__ __forceinline__ void shard_consts(
   *m1 = (z >> 7) | 1u;
 }
 
-template <typename T>
-__global__ void k_epoch_shard(const T* __restrict__ X, const T* __restrict__ Tg,
-                              T* __restrict__ xs, T* __restrict__ ts,
-                              int n, int K, int per_rank, int rank, int world,
-                              uint32_t k_mask, uint32_t c0, uint32_t m0,
-                              uint32_t c1, uint32_t m1) {
-  const int tid = blockIdx.x * blockDim.x + threadIdx.x;
-  const int cols = K + 1;
-  if (tid >= per_rank * cols) return;
-  const int i = tid / cols;
-  const int c = tid - i * cols;
-  const uint32_t p = (uint32_t)(rank + (size_t)i * world);
-  const uint32_t src = mix_bijection(p, k_mask, (uint32_t)n, c0, m0, c1, m1);
-  if (c < K) xs[(size_t)i * K + c] = X[(size_t)src * K + c];
-  else       ts[i] = Tg[src];
-}
-
-std::vector<torch::Tensor> epoch_shard(torch::Tensor X, torch::Tensor Tg,
-                                       int64_t seed, int64_t rank,
-                                       int64_t world) {
-  TORCH_CHECK(X.is_cuda() && X.is_contiguous() && Tg.is_contiguous());
-  const int n = (int)X.size(0), K = (int)X.size(1);
-  TORCH_CHECK(Tg.size(0) == n && Tg.size(1) == 1, "targets must be [n,1]");
-  const int per_rank = n / (int)world;
-  auto xs = at::empty({per_rank, K}, X.options());
-  auto ts = at::empty({per_rank, 1}, Tg.options());
-  uint32_t k_mask = 1;
-  while ((int64_t)k_mask + 1 < n) k_mask = (k_mask << 1) | 1u;
-  uint32_t c0, m0, c1, m1;
-  shard_consts((uint32_t)seed, &c0, &m0, &c1, &m1);
-  const int total = per_rank * (K + 1);
-  DISPATCH_F32_BF16(X.scalar_type(), "epoch_shard", {
-    hipLaunchKernelGGL((k_epoch_shard<scalar_t>), dim3(cdiv(total, 256)),
-                       dim3(256), 0, cur_stream(), cdptr<scalar_t>(X),
-                       cdptr<scalar_t>(Tg), dptr<scalar_t>(xs),
-                       dptr<scalar_t>(ts), n, K, per_rank, (int)rank,
-                       (int)world, k_mask, c0, m0, c1, m1);
-  });
-  HIP_OK(hipGetLastError());
-  return {xs, ts};
-}
-
-// Multi-EPOCH variant: one launch gathers `epochs` consecutive epoch
-// shards (seeds seed0, seed0+1, …) into one contiguous buffer pair —
-// block e of the output is bitwise-identical to epoch_shard(X, T,
-// seed0+e)'s result. This is what lets the persistent-engine deferral
-// span epoch boundaries (one multistep launch per ~max_defer steps
-// instead of one per epoch) and, as a side effect, gives this gather
-// kernel epochs× more workgroups to fill the 256 CUs with.
 template <typename T>
 __global__ void k_epoch_shard_multi(const T* __restrict__ X,
                                     const T* __restrict__ Tg,
@@ -815,7 +604,8 @@ __global__ void k_epoch_shard_multi(const T* __restrict__ X,
 std::vector<torch::Tensor> epoch_shard_multi(torch::Tensor X, torch::Tensor Tg,
                                              int64_t seed0, int64_t epochs,
                                              int64_t rank, int64_t world) {
-  TORCH_CHECK(X.is_cuda() && X.is_contiguous() && Tg.is_contiguous());
+  TORCH_CHECK(X.is_cuda() && Tg.is_cuda() && X.is_contiguous() &&
+              Tg.is_contiguous());
   TORCH_CHECK(epochs >= 1 && epochs <= 1 << 20, "epochs out of range");
   const int n = (int)X.size(0), K = (int)X.size(1);
   TORCH_CHECK(Tg.size(0) == n && Tg.size(1) == 1, "targets must be [n,1]");
@@ -835,6 +625,12 @@ std::vector<torch::Tensor> epoch_shard_multi(torch::Tensor X, torch::Tensor Tg,
   });
   HIP_OK(hipGetLastError());
   return {xs, ts};
+}
+
+std::vector<torch::Tensor> epoch_shard(torch::Tensor X, torch::Tensor Tg,
+                                       int64_t seed, int64_t rank,
+                                       int64_t world) {
+  return epoch_shard_multi(X, Tg, seed, 1, rank, world);
 }
 
 }  // namespace mi355x

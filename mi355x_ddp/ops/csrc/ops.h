@@ -1,6 +1,6 @@
 // Host-side launcher declarations for the MI355X (gfx950) kernel pack.
 // Implementations in kernels.hip, for the toy training-step family
-// (toy_fused_fwd_bwd, toy_multistep*) toy_kernels.hip, and for the stateful
+// (toy_fused_fwd_bwd, toy_multistep*) toy_kernels.hip, and for the
 // flat-bucket optimizers optim_kernels.hip; bound to Python in bindings.hip.
 #pragma once
 #include <torch/extension.h>
@@ -25,7 +25,7 @@ void linear_bwd_weight(torch::Tensor x, torch::Tensor dy,
 torch::Tensor linear_bwd_input(torch::Tensor dy, torch::Tensor w);
 
 // Standalone bf16 MFMA GEMM (v_mfma_f32_16x16x32_bf16, f32 accumulate):
-// y = x @ w^T + bias for larger bf16 shapes.
+// y = x @ w^T + bias. No model path routes to it; it is tested and timed.
 torch::Tensor gemm_bf16(torch::Tensor x, torch::Tensor w,
                         c10::optional<torch::Tensor> bias);
 
@@ -44,12 +44,14 @@ torch::Tensor mse_fwd(torch::Tensor y, torch::Tensor t);
 torch::Tensor mse_bwd(torch::Tensor y, torch::Tensor t, double grad_scale,
                       c10::optional<torch::Tensor> gout = c10::nullopt);
 
-// Fused SGD over a flat bucket: p -= lr*g; optionally g = 0 in the same
-// kernel (folds reference optimizer.step() + zero_grad, single_gpu.py:22,26).
+// Fused SGD over a flat bucket (optim_kernels.hip): p -= lr*g; optionally
+// g = 0 in the same kernel (folds reference optimizer.step() + zero_grad,
+// single_gpu.py:22,26). Like the stateful optimizers below it requires
+// device tensors of one dtype and length, padded and aligned to 4 elements.
 void sgd_flat(torch::Tensor param_flat, torch::Tensor grad_flat,
               double lr, bool zero_grad);
 
-// Momentum SGD over a flat bucket (optim_kernels.hip), torch.optim.SGD's
+// Momentum SGD over a flat bucket, torch.optim.SGD's
 // formula without dampening:
 //   d = g + wd*p; buf = mu*buf + d; d = nesterov ? d + mu*buf : buf;
 //   p -= lr*d; g = 0 when zero_grad.
@@ -77,8 +79,9 @@ void adamw_flat(torch::Tensor param_flat, torch::Tensor grad_flat,
 
 // Bucket gather/scatter ("flatten/unflatten"): one launch
 // moves every listed tensor <-> its segment of the flat bucket.
-// plan: int64 CPU tensor [n, 3] rows (src_ptr, bucket_elem_offset, numel)
-// prebuilt by the reducer; copied to device once and reused every step.
+// plan: int64 device tensor [blocks, 3], one row (tensor chunk address,
+// bucket byte offset, nbytes) per workgroup; build_copy_plan makes it once
+// on `device` and the reducer reuses it every step.
 torch::Tensor build_copy_plan(const std::vector<torch::Tensor>& tensors,
                               const std::vector<int64_t>& offsets,
                               torch::Device device);
@@ -104,7 +107,8 @@ std::vector<torch::Tensor> epoch_shard(torch::Tensor X, torch::Tensor Tg,
                                        int64_t world);
 
 // Multi-epoch form: gathers `epochs` consecutive shards (seeds seed0,
-// seed0+1, …) in ONE launch; block e is bitwise epoch_shard(seed0+e).
+// seed0+1, …) in ONE launch; block e is bitwise epoch_shard(seed0+e),
+// which is this call with epochs = 1.
 std::vector<torch::Tensor> epoch_shard_multi(torch::Tensor X, torch::Tensor Tg,
                                              int64_t seed0, int64_t epochs,
                                              int64_t rank, int64_t world);

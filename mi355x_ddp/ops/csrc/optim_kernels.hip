@@ -1,8 +1,10 @@
-// Stateful optimizers over one flat bucket: momentum SGD and AdamW.
+// Optimizers over one flat bucket: plain SGD, momentum SGD and AdamW.
 //
-// Both are memory-bound streaming kernels in the layout of k_sgd_flat_*:
-// 4 elements per lane (one float4, or one ushort4 of bf16), a grid capped
-// at kMaxBlocks with a grid-stride loop (guide G11), int64 indexing.
+// All are memory-bound streaming kernels in one layout: 4 elements per lane
+// (one float4, or one ushort4 of bf16; bucket lengths are padded to a
+// multiple of 4 by the reducer), int64 indexing. Plain SGD takes one vector
+// per thread on an uncapped grid; the stateful kernels cap the grid at
+// kMaxBlocks and walk a grid-stride loop (guide G11).
 // Parameters and gradients are f32 or bf16; optimizer state is always f32.
 // bf16 does the arithmetic in f32 and rounds to nearest once, on the
 // parameter store — there are no f32 master weights.
@@ -69,6 +71,20 @@ __device__ __forceinline__ void zero4(__hip_bfloat16* p, int64_t i) {
 }
 
 }  // namespace
+
+// Plain SGD (+ fold zero_grad): p -= lr*g as one fma; g = 0.
+template <typename T>
+__global__ void k_sgd_flat(T* __restrict__ p, T* __restrict__ g, float lr,
+                           int64_t n4, int zero) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n4) return;
+  const F4 gv = ld4(g, i);
+  F4 pv = ld4(p, i);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) pv.v[j] = __builtin_fmaf(-lr, gv.v[j], pv.v[j]);
+  st4(p, i, pv);
+  if (zero) zero4(g, i);
+}
 
 // d = g + wd*p; buf = mu*buf + d; d = nesterov ? d + mu*buf : buf;
 // p -= lr*d. buf == nullptr is momentum 0 (weight decay only).
@@ -206,6 +222,19 @@ dim3 flat_grid(int64_t n4) {
 }
 
 }  // namespace
+
+void sgd_flat(torch::Tensor param_flat, torch::Tensor grad_flat, double lr,
+              bool zero_grad) {
+  const int64_t n4 = check_flat(param_flat, grad_flat, "sgd_flat");
+  if (n4 == 0) return;
+  DISPATCH_F32_BF16(param_flat.scalar_type(), "sgd_flat", {
+    hipLaunchKernelGGL((k_sgd_flat<scalar_t>), dim3(cdiv(n4, kThreads)),
+                       dim3(kThreads), 0, cur_stream(),
+                       dptr<scalar_t>(param_flat), dptr<scalar_t>(grad_flat),
+                       (float)lr, n4, zero_grad ? 1 : 0);
+  });
+  HIP_OK(hipGetLastError());
+}
 
 void sgd_momentum_flat(torch::Tensor param_flat, torch::Tensor grad_flat,
                        c10::optional<torch::Tensor> buf, double lr,

@@ -6,9 +6,9 @@ reference's torch.optim.SGD(lr=1e-3) (single_gpu.py:51).
 - Bucketed params (marked by the Reducer): ONE hand-written HIP kernel per
   bucket does the update AND zeroes the flat grad (SURVEY §2.2 N8+N9 —
   optimizer.step + zero_grad in one launch). momentum == weight_decay == 0
-  runs `k_sgd_flat_*` (p -= lr*g) and allocates no state; anything else
+  runs `k_sgd_flat` (p -= lr*g) and allocates no state; anything else
   runs `k_sgd_momentum_flat`, its momentum buffer a flat fp32 buffer per
-  bucket.
+  bucket. Both are in ops/csrc/optim_kernels.hip.
 - Un-bucketed params: the same formula per parameter (CPU plumbing path
   and models trained without the DDP engine).
 

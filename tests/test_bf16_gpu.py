@@ -29,6 +29,18 @@ def test_linear_fwd_bf16(B, K, N):
     assert torch.allclose(y.cpu().float(), ref, atol=3e-2, rtol=3e-2)
 
 
+# (33, 21, 7) takes the split path, (65, ...) the serial one, in both
+# orientations of its short side (dX contracts over N, writes K columns)
+@pytest.mark.parametrize("B,K,N", [(33, 21, 7), (65, 5, 17), (65, 17, 5)])
+def test_linear_bwd_input_bf16(B, K, N):
+    dy = (_rand(B, N, seed=13) - 0.5).to(DEV).bfloat16()
+    w = (_rand(N, K, seed=14) - 0.5).to(DEV).bfloat16()
+    dx = ops.ext().linear_bwd_input(dy, w)
+    assert dx.dtype == torch.bfloat16 and dx.shape == (B, K)
+    ref = dy.cpu().float() @ w.cpu().float()
+    assert torch.allclose(dx.cpu().float(), ref, atol=3e-2, rtol=3e-2)
+
+
 @pytest.mark.parametrize("B,K,N", [(32, 32, 16), (64, 100, 48), (16, 20, 1),
                                    (128, 256, 256)])
 def test_gemm_bf16_mfma(B, K, N):

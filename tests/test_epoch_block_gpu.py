@@ -32,6 +32,23 @@ def test_epoch_shard_multi_blocks_bitwise(world, epochs, seed0):
             xs, ts = _ext().epoch_shard(X, T, seed0 + e, rank, world)
             assert torch.equal(xs_m[e * per:(e + 1) * per], xs)
             assert torch.equal(ts_m[e * per:(e + 1) * per], ts)
+    if (world, epochs) != (2, 3):
+        return
+    # epoch_shard is epoch_shard_multi with epochs == 1, so the comparison
+    # above is of one kernel with itself: hold every block to the Python
+    # mirror of the permutation as well
+    from mi355x_ddp import ops
+    n, K = 256, 3
+    X = torch.rand(n, K, device="cuda")
+    T = torch.rand(n, 1, device="cuda")
+    per = n // world
+    for rank in range(world):
+        xs_m, ts_m = _ext().epoch_shard_multi(X, T, seed0, epochs, rank, world)
+        for e in range(epochs):
+            idx = torch.tensor([ops.perm_index(seed0 + e, rank + i * world, n)
+                                for i in range(per)], device="cuda")
+            assert torch.equal(xs_m[e * per:(e + 1) * per], X[idx])
+            assert torch.equal(ts_m[e * per:(e + 1) * per], T[idx])
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])

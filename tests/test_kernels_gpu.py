@@ -25,8 +25,11 @@ def test_ext_loads_natively():
     assert "_C" in C.__file__ and "mi355x_ddp" in C.__file__
 
 
+# (65, 5, 17): the serial path with a ragged last M tile, a contraction
+# shorter than one 16-wide tile and ragged output columns.
 @pytest.mark.parametrize("B,K,N", [(32, 20, 1), (32, 20, 16), (33, 21, 7),
-                                   (128, 64, 48), (256, 100, 1000)])
+                                   (128, 64, 48), (256, 100, 1000),
+                                   (65, 5, 17)])
 def test_linear_fwd(B, K, N):
     x = _rand(B, K, seed=1).to(DEV)
     w = _rand(N, K, seed=2).to(DEV) - 0.3
@@ -53,7 +56,15 @@ def test_linear_bwd_weight(B, K, N):
     assert torch.allclose(db.cpu(), 2 * ref_b, atol=1e-4, rtol=1e-4)
 
 
-@pytest.mark.parametrize("B,K,N", [(32, 20, 1), (33, 21, 7), (64, 128, 32)])
+# dX contracts over N and writes K columns. (65, 17, 5) is the serial path
+# with a ragged last M tile, a contraction shorter than one 16-wide tile
+# and ragged output columns; (17, 40, 3) the split path with a slice per
+# wave so small that waves 1-3 get an empty one, and three output tiles
+# across. Each is also run with K and N swapped: (65, 5, 17) has a
+# contraction one past a tile, (17, 3, 40) a ragged last slice.
+@pytest.mark.parametrize("B,K,N", [(32, 20, 1), (33, 21, 7), (64, 128, 32),
+                                   (65, 17, 5), (65, 5, 17),
+                                   (17, 40, 3), (17, 3, 40)])
 def test_linear_bwd_input(B, K, N):
     dy = (_rand(B, N, seed=6) - 0.5).to(DEV)
     w = (_rand(N, K, seed=7) - 0.5).to(DEV)

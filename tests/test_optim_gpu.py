@@ -215,6 +215,30 @@ def test_weight_decay_only_sgd_needs_no_buffer():
         ops.sgd_momentum_flat_(p, g, None, LR_SGD, 0.9, WD, False)
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_plain_sgd_equals_momentum_kernel_bitwise(dtype):
+    """k_sgd_flat is the one fma of k_sgd_momentum_flat without momentum or
+    decay (which is itself held bitwise to torch.optim above)."""
+    p, g, _, _ = (x.to(DEV) for x in _inputs("sgd", dtype, 1024, 1))
+    p2, g2 = p.clone(), g.clone()
+    ops.ext().sgd_flat(p, g, LR_SGD, True)
+    ops.ext().sgd_momentum_flat(p2, g2, None, LR_SGD, 0, 0, False, True)
+    assert not torch.equal(p, _inputs("sgd", dtype, 1024, 1)[0].to(DEV))
+    assert torch.equal(p, p2)
+    assert not g.any() and not g2.any()
+
+
+def test_plain_sgd_rejects_mismatched_and_misaligned_buffers():
+    base = torch.ones(1032, device=DEV)
+    g = torch.ones(1024, device=DEV)
+    with pytest.raises(RuntimeError, match="length"):
+        ops.ext().sgd_flat(base[:1028], g, 0.5, True)
+    with pytest.raises(RuntimeError, match="aligned"):
+        ops.ext().sgd_flat(base[1:1025], g, 0.5, True)  # 4 B past 16 B
+    torch.cuda.synchronize()
+    assert bool((base == 1).all()) and bool((g == 1).all())  # nothing ran
+
+
 # ---------------------------------------------------------------------------
 # attached optimizers vs torch.optim on the device
 # ---------------------------------------------------------------------------

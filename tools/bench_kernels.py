@@ -63,6 +63,10 @@ def main():
     row("linear bwd dX 32x1000x2048 (split-N)",
         timeit(lambda: ops.ext().linear_bwd_input(dy, wf)),
         timeit(lambda: dy @ wf), "")
+    dy128 = torch.rand(128, 1000, device=DEV)
+    row("linear bwd dX 128x1000x2048 (serial)",
+        timeit(lambda: ops.ext().linear_bwd_input(dy128, wf)),
+        timeit(lambda: dy128 @ wf), "")
 
     # FC dW: 1000x32 @ 32x2048
     dw = torch.empty(1000, 2048, device=DEV)
@@ -101,6 +105,11 @@ def main():
     row("SGD+zero_grad 25 MB bucket",
         timeit(lambda: ops.ext().sgd_flat(p, g, 1e-3, True)),
         timeit(lambda: (p.add_(g, alpha=-1e-3), g.zero_())),
+        "1 launch vs 2")
+    p16, g16 = p.bfloat16(), g.bfloat16()
+    row("SGD+zero_grad bf16, same bucket (12.5 MB)",
+        timeit(lambda: ops.ext().sgd_flat(p16, g16, 1e-3, True)),
+        timeit(lambda: (p16.add_(g16, alpha=-1e-3), g16.zero_())),
         "1 launch vs 2")
 
     # epoch shard vs randperm+index
