@@ -153,8 +153,12 @@ class DevicePrefetcher:
     def __init__(self, loader, device: torch.device):
         self.loader = loader
         self.device = device
-        self._stream = (torch.cuda.Stream(device=device)
-                        if device.type == "cuda" else None)
+        self._stream = None
+        if device.type == "cuda":
+            # not a bare torch.cuda.Stream(): after a failed graph capture
+            # one pool stream is unusable (engine._DEAD_STREAMS)
+            from .engine import side_stream
+            self._stream = side_stream(device)
 
     def __len__(self) -> int:
         return len(self.loader)

@@ -42,6 +42,22 @@ _CAPTURE_POISONED = False
 # Graphs whose capture failed are LEAKED on purpose: destroying them can
 # terminate the process (above). A handful of small host objects.
 _DEAD_GRAPHS = []
+# Capture streams of failed captures. The stream stays in the invalidated
+# capture state: every later operation on it fails with
+# hipErrorStreamCaptureInvalidated ("operation failed due to a previous
+# error during capture"). torch hands its 32 pool streams out round-robin,
+# so the dead one comes round again to whoever asks for a stream next.
+_DEAD_STREAMS = []
+
+
+def side_stream(device=None) -> "torch.cuda.Stream":
+    """torch.cuda.Stream(device), skipping the capture stream of a failed
+    capture (see _DEAD_STREAMS)."""
+    for _ in range(64):  # the pool holds 32 streams
+        s = torch.cuda.Stream(device=device)
+        if not any(s == d for d in _DEAD_STREAMS):
+            return s
+    raise RuntimeError("every pool stream belongs to a failed capture")
 
 
 def _poison_captures(graph):
@@ -59,6 +75,7 @@ def _recover_failed_capture(ctx):
     stream, allocations routed to the dead graph pool, and
     hipErrorStreamCaptureInvalidated latched in HIP's thread state.
     Undo all three so the eager fallback can proceed."""
+    _DEAD_STREAMS.append(ctx.capture_stream)
     try:
         ctx.stream_ctx.__exit__(None, None, None)
     except Exception:
@@ -348,7 +365,7 @@ class GraphedAutogradStep:
         before the first capture (allocator + autograd engine initialize
         lazily-created state off-capture). These steps train for real —
         on the first batch, like any warmup."""
-        s = torch.cuda.Stream()
+        s = side_stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             for _ in range(self.warmup_steps):

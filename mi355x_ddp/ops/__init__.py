@@ -2,8 +2,8 @@
 
 Every op has two paths:
 - device tensors -> the hand-written CDNA4 HIP kernels in `mi355x_ddp._C`
-  (MFMA-tiled linear, CE/MSE, fused SGD / momentum SGD / AdamW, bucket
-  copies). If the extension
+  (MFMA-tiled linear, CE/MSE, fused SGD / momentum SGD / AdamW, global
+  grad-norm clipping, bucket copies). If the extension
   is missing on a GPU host this layer raises — there is NO silent eager
   fallback on the GPU.
 - CPU tensors -> plain PyTorch reference implementations, used by the
@@ -143,13 +143,84 @@ def mse_loss(output: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
 # ---------------------------------------------------------------------------
 # Flat-bucket primitives used by the reducer / fused optimizer
 # ---------------------------------------------------------------------------
+_SUMSQ_THREADS, _SUMSQ_MAX_BLOCKS = 256, 2048  # optim_kernels.hip
+
+
+def sumsq_slots(numel: int) -> int:
+    """How many float64 partials `grad_sumsq_flat_` writes for a bucket of
+    `numel` elements: one per block of k_sumsq_flat's grid."""
+    if numel < 0 or numel % 4:
+        raise ValueError("sumsq_slots: bucket length must be padded to a "
+                         "multiple of 4")
+    blocks = (numel // 4 + _SUMSQ_THREADS - 1) // _SUMSQ_THREADS
+    return min(max(blocks, 1), _SUMSQ_MAX_BLOCKS)
+
+
+def grad_sumsq_flat_(grad_flat: torch.Tensor, partials: torch.Tensor) -> None:
+    """Sum of squares of one flat gradient bucket, as `sumsq_slots(numel)`
+    float64 partial sums written into `partials` (usually a slice of the
+    optimizer's buffer). Every slot is overwritten on every call; their sum
+    is the bucket's contribution to the squared global L2 norm. fp32 or
+    bf16 gradients; a lane squares and adds in fp32, the rest is float64.
+
+    The CPU mirror puts the whole float64 sum into slot 0 and zeros into
+    the rest."""
+    if partials.dtype != torch.float64 \
+            or partials.numel() != sumsq_slots(grad_flat.numel()):
+        raise ValueError("grad_sumsq_flat_: partials must be float64 with "
+                         "exactly sumsq_slots(numel) elements")
+    if grad_flat.is_cuda:
+        ext().grad_sumsq_flat(grad_flat, partials)
+        return
+    partials.zero_()
+    partials[0] = grad_flat.double().square().sum()
+
+
+def clip_coef_(partials: torch.Tensor, clip_state: torch.Tensor,
+               max_norm: float) -> None:
+    """From every bucket's partials (one float64 tensor, summed in a fixed
+    order) to `clip_state`, float32[2]:
+
+        clip_state[0] = total_norm = float32(sqrt(sum))
+        clip_state[1] = coef = min(1, max_norm / (total_norm + 1e-6))
+
+    the coefficient in torch.nn.utils.clip_grad_norm_'s own fp32 operation
+    sequence (a reciprocal, a multiplication, clamp(max=1)), so a NaN norm
+    gives a NaN coefficient and an infinite one gives 0. Called once per
+    optimizer step after every `grad_sumsq_flat_`; `clip_state[1:2]` is the
+    `grad_scale` of the update ops. The CPU mirror evaluates the same
+    formula on fp32 tensors."""
+    if partials.is_cuda:
+        ext().clip_coef(partials, clip_state, max_norm)
+        return
+    norm = partials.sum().sqrt().to(torch.float32)
+    clip_state[0] = norm
+    clip_state[1] = torch.clamp((norm + 1e-6).reciprocal() * max_norm,
+                                max=1.0)
+
+
+def _scaled(g: torch.Tensor, grad_scale: torch.Tensor) -> torch.Tensor:
+    """What grad.mul_(coef) would have stored, without storing it."""
+    return (g.float() * grad_scale).to(g.dtype)
+
+
 def sgd_flat_(param_flat: torch.Tensor, grad_flat: torch.Tensor, lr: float,
-              zero_grad: bool = True) -> None:
-    """p -= lr*g over a flat bucket, grad zeroing folded in (SURVEY N8+N9)."""
+              zero_grad: bool = True,
+              grad_scale: Optional[torch.Tensor] = None) -> None:
+    """p -= lr*g over a flat bucket, grad zeroing folded in (SURVEY N8+N9).
+
+    `grad_scale` (here and in the two stateful updates below): a float32
+    tensor of 1 element on the bucket's device, the clip coefficient from
+    `clip_coef_`. The update then uses g * grad_scale, one fp32 multiply
+    (for bf16 rounded to bf16 and widened again: what `grad.mul_(coef)`
+    would have stored). The scaled value is NOT written back: with
+    zero_grad the gradient is zeroed, with zero_grad=False it is left
+    UNSCALED."""
     if param_flat.is_cuda:
-        ext().sgd_flat(param_flat, grad_flat, lr, zero_grad)
+        ext().sgd_flat(param_flat, grad_flat, lr, zero_grad, grad_scale)
     else:
-        param_flat.add_(grad_flat, alpha=-lr)
+        g = grad_flat if grad_scale is None else _scaled(grad_flat, grad_scale)
+        param_flat.add_(g, alpha=-lr)
         if zero_grad:
             grad_flat.zero_()
 
@@ -163,7 +234,8 @@ def sgd_momentum_flat_(param_flat: torch.Tensor, grad_flat: torch.Tensor,
                        buf: Optional[torch.Tensor], lr: float,
                        momentum: float = 0.0, weight_decay: float = 0.0,
                        nesterov: bool = False,
-                       zero_grad: bool = True) -> None:
+                       zero_grad: bool = True,
+                       grad_scale: Optional[torch.Tensor] = None) -> None:
     """torch.optim.SGD's update (no dampening) over a flat bucket, grad
     zeroing folded in:
 
@@ -174,7 +246,7 @@ def sgd_momentum_flat_(param_flat: torch.Tensor, grad_flat: torch.Tensor,
     reproduces torch's first-step `buf = d` with no step count. `buf=None`
     requires momentum 0 (weight decay only). bf16 parameters: arithmetic in
     fp32, ONE round-to-nearest on the parameter store; there are no fp32
-    master weights (as with sgd_flat_).
+    master weights (as with sgd_flat_). `grad_scale`: see sgd_flat_.
 
     The CPU path is the same operation sequence as torch's single-tensor
     SGD, in fp32; it is the numerics reference for the kernel."""
@@ -182,9 +254,10 @@ def sgd_momentum_flat_(param_flat: torch.Tensor, grad_flat: torch.Tensor,
         raise ValueError("sgd_momentum_flat_: momentum needs a buffer")
     if param_flat.is_cuda:
         ext().sgd_momentum_flat(param_flat, grad_flat, buf, lr, momentum,
-                                weight_decay, nesterov, zero_grad)
+                                weight_decay, nesterov, zero_grad, grad_scale)
         return
-    sgd_momentum_reference_(param_flat, grad_flat, buf, lr, momentum,
+    g = grad_flat if grad_scale is None else _scaled(grad_flat, grad_scale)
+    sgd_momentum_reference_(param_flat, g, buf, lr, momentum,
                             weight_decay, nesterov)
     if zero_grad:
         grad_flat.zero_()
@@ -227,7 +300,8 @@ def adamw_flat_(param_flat: torch.Tensor, grad_flat: torch.Tensor,
                 step, lr: float, beta1: float, beta2: float, eps: float,
                 weight_decay: float,
                 decay_mask: Optional[torch.Tensor] = None,
-                zero_grad: bool = True) -> None:
+                zero_grad: bool = True,
+                grad_scale: Optional[torch.Tensor] = None) -> None:
     """torch.optim.AdamW's update over a flat bucket at step count t, grad
     zeroing folded in:
 
@@ -240,7 +314,7 @@ def adamw_flat_(param_flat: torch.Tensor, grad_flat: torch.Tensor,
     group never straddles two); a zero byte exempts the group from decay.
     State is fp32 whatever the parameter dtype. bf16 parameters: arithmetic
     in fp32, ONE round-to-nearest on the parameter store; there are no fp32
-    master weights.
+    master weights. `grad_scale`: see sgd_flat_.
 
     `step`: on the GPU the int32 device tensor that `adamw_tick_` has
     ALREADY advanced for this step (the kernel never sees a host count, so
@@ -252,9 +326,10 @@ def adamw_flat_(param_flat: torch.Tensor, grad_flat: torch.Tensor,
     if param_flat.is_cuda:
         ext().adamw_flat(param_flat, grad_flat, exp_avg, exp_avg_sq, step,
                          lr, beta1, beta2, eps, weight_decay, decay_mask,
-                         zero_grad)
+                         zero_grad, grad_scale)
         return
-    adamw_reference_(param_flat, grad_flat, exp_avg, exp_avg_sq, int(step),
+    g = grad_flat if grad_scale is None else _scaled(grad_flat, grad_scale)
+    adamw_reference_(param_flat, g, exp_avg, exp_avg_sq, int(step),
                      lr, beta1, beta2, eps, weight_decay,
                      None if decay_mask is None
                      else _expand_mask(decay_mask, param_flat.numel()))

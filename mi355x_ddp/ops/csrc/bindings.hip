@@ -39,19 +39,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mse_bwd", &mi355x::mse_bwd, py::arg("y"), py::arg("t"),
         py::arg("grad_scale"), py::arg("gout") = c10::nullopt);
   m.def("sgd_flat", &mi355x::sgd_flat, py::arg("param_flat"),
-        py::arg("grad_flat"), py::arg("lr"), py::arg("zero_grad") = true);
+        py::arg("grad_flat"), py::arg("lr"), py::arg("zero_grad") = true,
+        py::arg("grad_scale") = c10::nullopt);
   m.def("sgd_momentum_flat", &mi355x::sgd_momentum_flat,
         py::arg("param_flat"), py::arg("grad_flat"), py::arg("buf"),
         py::arg("lr"), py::arg("momentum") = 0.0,
         py::arg("weight_decay") = 0.0, py::arg("nesterov") = false,
-        py::arg("zero_grad") = true);
+        py::arg("zero_grad") = true, py::arg("grad_scale") = c10::nullopt);
   m.def("adamw_tick", &mi355x::adamw_tick, py::arg("step_state"),
         py::arg("lr"), py::arg("beta1"), py::arg("beta2"));
   m.def("adamw_flat", &mi355x::adamw_flat, py::arg("param_flat"),
         py::arg("grad_flat"), py::arg("exp_avg"), py::arg("exp_avg_sq"),
         py::arg("step_state"), py::arg("lr"), py::arg("beta1"),
         py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"),
-        py::arg("decay_mask") = c10::nullopt, py::arg("zero_grad") = true);
+        py::arg("decay_mask") = c10::nullopt, py::arg("zero_grad") = true,
+        py::arg("grad_scale") = c10::nullopt);
+  m.def("sumsq_slots", &mi355x::sumsq_slots, py::arg("numel"));
+  m.def("grad_sumsq_flat", &mi355x::grad_sumsq_flat, py::arg("grad_flat"),
+        py::arg("partials"));
+  m.def("clip_coef", &mi355x::clip_coef, py::arg("partials"),
+        py::arg("clip_state"), py::arg("max_norm"));
   m.def("build_copy_plan",
         [](const std::vector<torch::Tensor>& tensors,
            const std::vector<int64_t>& offsets, int device) {

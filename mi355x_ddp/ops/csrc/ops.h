@@ -48,8 +48,13 @@ torch::Tensor mse_bwd(torch::Tensor y, torch::Tensor t, double grad_scale,
 // g = 0 in the same kernel (folds reference optimizer.step() + zero_grad,
 // single_gpu.py:22,26). Like the stateful optimizers below it requires
 // device tensors of one dtype and length, padded and aligned to 4 elements.
+// grad_scale (all three update ops): optional f32[1] device tensor, the
+// clip coefficient of clip_coef below. With it the update uses g * coef
+// (for bf16 rounded to bf16, as grad.mul_(coef) would store it); g itself
+// is not rewritten — zeroed with zero_grad, left UNSCALED without.
 void sgd_flat(torch::Tensor param_flat, torch::Tensor grad_flat,
-              double lr, bool zero_grad);
+              double lr, bool zero_grad,
+              c10::optional<torch::Tensor> grad_scale = c10::nullopt);
 
 // Momentum SGD over a flat bucket, torch.optim.SGD's
 // formula without dampening:
@@ -61,7 +66,8 @@ void sgd_flat(torch::Tensor param_flat, torch::Tensor grad_flat,
 void sgd_momentum_flat(torch::Tensor param_flat, torch::Tensor grad_flat,
                        c10::optional<torch::Tensor> buf, double lr,
                        double momentum, double weight_decay, bool nesterov,
-                       bool zero_grad);
+                       bool zero_grad,
+                       c10::optional<torch::Tensor> grad_scale = c10::nullopt);
 
 // AdamW over a flat bucket with the step count on the device, so that a
 // captured graph advances it on replay. step_state is int32[4]:
@@ -75,7 +81,21 @@ void adamw_flat(torch::Tensor param_flat, torch::Tensor grad_flat,
                 torch::Tensor exp_avg, torch::Tensor exp_avg_sq,
                 torch::Tensor step_state, double lr, double beta1,
                 double beta2, double eps, double weight_decay,
-                c10::optional<torch::Tensor> decay_mask, bool zero_grad);
+                c10::optional<torch::Tensor> decay_mask, bool zero_grad,
+                c10::optional<torch::Tensor> grad_scale = c10::nullopt);
+
+// Global grad-norm clipping over the flat buckets. grad_sumsq_flat leaves
+// one f64 partial sum of squares per block in `partials`, which must have
+// exactly sumsq_slots(numel) elements, all rewritten on every call (no
+// atomics, nothing to pre-zero). clip_coef, once per step after every
+// bucket's grad_sumsq_flat, sums all of `partials` (the buckets' segments
+// side by side) in a fixed order and writes clip_state (f32[2]):
+//   [0] total_norm = sqrt(sum), [1] coef = min(1, max_norm/(norm + 1e-6))
+// in torch.nn.utils.clip_grad_norm_'s own f32 operation sequence.
+int64_t sumsq_slots(int64_t numel);
+void grad_sumsq_flat(torch::Tensor grad_flat, torch::Tensor partials);
+void clip_coef(torch::Tensor partials, torch::Tensor clip_state,
+               double max_norm);
 
 // Bucket gather/scatter ("flatten/unflatten"): one launch
 // moves every listed tensor <-> its segment of the flat bucket.

@@ -1,5 +1,5 @@
 """Native data-parallel engine: communicator, reducer, DDP wrapper, fused
-optimizers (§2.3 — DP is the reference's one
+optimizers with built-in global grad-norm clipping (§2.3 — DP is the reference's one
 parallelism strategy, re-implemented here from scratch for MI355X)."""
 
 from .comm import (ddp_setup, create_comm, GlooComm,  # noqa: F401

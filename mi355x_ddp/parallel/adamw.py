@@ -24,9 +24,13 @@ keep the exemption. And a load writes into the existing flat buffers and the
 existing device counter, so a step already captured in a graph keeps
 working; a changed `lr` or other hyper-parameter still needs a recapture.
 `eps` must be positive: with 0 the zero padding of the buckets would
-compute 0/0. Limits: see flat_optim.py — single param_group when attached,
+compute 0/0. `max_grad_norm` clips by the global L2 norm inside the step
+(flat_optim.py); within a step the order is clip launches, tick, bucket
+kernels. Limits: see flat_optim.py — single param_group when attached,
 host-scalar lr (a scheduler needs a recapture under graph capture), no
-fp32 master weights for bf16; no amsgrad, no maximize.
+fp32 master weights for bf16; no amsgrad, no maximize; clipping by the
+global L2 norm only (no other norm, no error_if_nonfinite), and
+`max_grad_norm`, like `no_decay_params`, is not part of `state_dict()`.
 """
 
 from __future__ import annotations
@@ -45,7 +49,8 @@ class FusedAdamW(FlatBucketOptimizer):
     def __init__(self, params: Iterable[torch.nn.Parameter], lr: float = 1e-3,
                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 1e-2,
-                 no_decay_params: Optional[Iterable[torch.nn.Parameter]] = None):
+                 no_decay_params: Optional[Iterable[torch.nn.Parameter]] = None,
+                 max_grad_norm: Optional[float] = None):
         if lr <= 0:
             raise ValueError(f"invalid lr {lr}")
         if eps <= 0:
@@ -60,7 +65,8 @@ class FusedAdamW(FlatBucketOptimizer):
         super().__init__(params, dict(
             lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay,
             amsgrad=False, maximize=False, foreach=None, capturable=False,
-            differentiable=False, fused=None, decoupled_weight_decay=True))
+            differentiable=False, fused=None, decoupled_weight_decay=True),
+            max_grad_norm=max_grad_norm)
         self._no_decay = {id(p) for p in (no_decay_params or ())}
         self._step_state = None  # int32[4], see ops.adamw_tick_
         self._decay_masks = None
@@ -123,6 +129,7 @@ class FusedAdamW(FlatBucketOptimizer):
             with torch.enable_grad():
                 loss = closure()
         self._check_fenced()
+        scale = self._clip()  # loose grads are scaled in place there
         g0 = self.param_groups[0]
         ss = self._steps(g0["params"][0].device)
         # one tick per step, ahead of every bucket update
@@ -136,7 +143,8 @@ class FusedAdamW(FlatBucketOptimizer):
                     flat_param, flat_grad, m[bi], v[bi], step, g0["lr"], b1,
                     b2, g0["eps"], g0["weight_decay"],
                     None if self._decay_masks is None
-                    else self._decay_masks[bi], zero_grad=True)
+                    else self._decay_masks[bi], zero_grad=True,
+                    grad_scale=scale)
         t = None
         for group in self.param_groups:
             b1, b2 = group["betas"]

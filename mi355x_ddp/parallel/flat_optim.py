@@ -7,20 +7,41 @@ state lives in fp32 flat buffers of the same layout, one per bucket;
 `self.state[p]` holds per-parameter VIEWS of them. Un-attached (or for
 parameters outside every bucket) the same formula runs per parameter.
 
+`max_grad_norm` clips the gradient by its global L2 norm over all of the
+optimizer's parameters, as torch.nn.utils.clip_grad_norm_ does between
+backward() and step(), but inside the step: one read pass per bucket for
+the norm (`ops.grad_sumsq_flat_`), one `ops.clip_coef_`, and the
+coefficient folded into the update kernels, which read every gradient
+anyway. Nothing is read back to the host, so an attached step still
+captures into a hipGraph; every rank computes the same bits from the same
+averaged buckets, so no collective is needed. `opt.grad_norm` /
+`opt.clip_coef` are device views of the last step's pre-clip norm and
+coefficient (reading them is the caller's sync). The total norm is fp32
+whatever the gradient dtype (torch returns bf16 for bf16 gradients).
+Non-finite gradients behave as torch's default error_if_nonfinite=False:
+a NaN norm gives a NaN coefficient, an infinite one gives 0 (and inf * 0 =
+NaN at the offending element).
+
 Limits shared by the subclasses:
 - attached, a single param_group: a bucket takes one set of hyper-parameters;
 - `lr` is a host scalar: whole-step graph capture bakes it in, so a
   scheduler that changes it needs a recapture;
 - bf16 parameters are updated in fp32 arithmetic with one rounding on the
-  store; there are no fp32 master weights.
+  store; there are no fp32 master weights;
+- clipping is by the global L2 norm only: no other norm type, no
+  error_if_nonfinite, no per-group clipping. `max_grad_norm` is an
+  attribute, not a param-group key, and not part of `state_dict()`.
 """
 
 from __future__ import annotations
 
+import math
 import os
-from typing import Dict, Iterable, List
+from typing import Dict, Iterable, List, Optional
 
 import torch
+
+from .. import ops
 
 
 class FlatBucketOptimizer(torch.optim.Optimizer):
@@ -28,12 +49,112 @@ class FlatBucketOptimizer(torch.optim.Optimizer):
     # under torch.optim's own state keys (state_dict interchange)
     _state_keys: tuple = ()
 
-    def __init__(self, params: Iterable[torch.nn.Parameter], defaults: dict):
+    def __init__(self, params: Iterable[torch.nn.Parameter], defaults: dict,
+                 max_grad_norm: Optional[float] = None):
         super().__init__(params, defaults)
         self._flat_pairs = None  # bound by attach_reducer
         self._bucketed = set()
         self._reducer = None
         self._flat_state: Dict[str, List[torch.Tensor]] = {}
+        # clipping: float64 partial sums of squares, the buckets' segments
+        # side by side plus one trailing slot for the loose parameters,
+        # and float32 [total_norm, coef]; allocated on first need, reused
+        self._clip_partials = None
+        self._clip_segments = None  # per bucket (lo, hi); None = rebind
+        self._loose_slot_used = False
+        self._clip_state = None
+        self._clipped = False  # a clipped step has run
+        self.max_grad_norm = max_grad_norm
+
+    # -- global grad-norm clipping -------------------------------------------
+    @property
+    def max_grad_norm(self) -> Optional[float]:
+        return self._max_grad_norm
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, value: Optional[float]) -> None:
+        if value is not None:
+            value = float(value)
+            if not (math.isfinite(value) and value > 0):
+                raise ValueError(f"invalid max_grad_norm {value}: a positive "
+                                 "finite number, or None for no clipping")
+        self._max_grad_norm = value
+
+    @property
+    def grad_norm(self) -> Optional[torch.Tensor]:
+        """Pre-clip global L2 norm of the most recent clipped step: a 0-dim
+        float32 view on the device; None before the first such step."""
+        return self._clip_state[0] if self._clipped else None
+
+    @property
+    def clip_coef(self) -> Optional[torch.Tensor]:
+        """The coefficient the most recent clipped step scaled its
+        gradients by, min(1, max_grad_norm / (grad_norm + 1e-6))."""
+        return self._clip_state[1] if self._clipped else None
+
+    def _bind_clip_buffers(self, device) -> None:
+        """(Re)allocate the clip buffers unless they already fit the bucket
+        layout on `device` — kept across a repeated attach or a
+        load_state_dict, like the flat state, so that a captured graph
+        stays valid."""
+        sizes = [] if self._flat_pairs is None else \
+            [ops.sumsq_slots(fg.numel()) for _, fg in self._flat_pairs]
+        total = sum(sizes) + 1
+        have = self._clip_partials
+        if have is None or have.numel() != total or have.device != device:
+            self._clip_partials = torch.zeros(total, dtype=torch.float64,
+                                              device=device)
+            self._loose_slot_used = False
+        if self._clip_state is None or self._clip_state.device != device:
+            self._clip_state = torch.zeros(2, dtype=torch.float32,
+                                           device=device)
+            self._clipped = False
+        self._clip_segments, lo = [], 0
+        for n in sizes:
+            self._clip_segments.append((lo, lo + n))
+            lo += n
+
+    def _clip(self) -> Optional[torch.Tensor]:
+        """With max_grad_norm set: compute the global norm and the clip
+        coefficient on the device, scale the loose gradients in place and
+        return the 1-element grad_scale the bucket updates take. None when
+        clipping is off."""
+        if self._max_grad_norm is None:
+            return None
+        loose = [p for g in self.param_groups for p in self._loose_params(g)]
+        if self._flat_pairs:
+            device = self._flat_pairs[0][0].device
+        else:
+            device = self.param_groups[0]["params"][0].device
+        if self._clip_segments is None \
+                or self._clip_partials.device != device:
+            self._bind_clip_buffers(device)
+        partials = self._clip_partials
+        if self._flat_pairs is not None:
+            for (lo, hi), (_, flat_grad) in zip(self._clip_segments,
+                                                self._flat_pairs):
+                ops.grad_sumsq_flat_(flat_grad, partials[lo:hi])
+        # the trailing slot: the loose parameters' sum of squares; zero
+        # from the allocation on, so a fully bucketed model never writes it
+        if loose:
+            partials[-1:].copy_(torch.stack(
+                [p.grad.double().square().sum().to(device)
+                 for p in loose]).sum(0, keepdim=True))
+            self._loose_slot_used = True
+        elif self._loose_slot_used:
+            partials[-1:].zero_()
+            self._loose_slot_used = False
+        ops.clip_coef_(partials, self._clip_state, self._max_grad_norm)
+        self._clipped = True
+        scale = self._clip_state[1:2]
+        for p in loose:
+            # the 1-ELEMENT view, not the 0-dim one: torch's type promotion
+            # would cast a 0-dim coefficient to a bf16 gradient's dtype
+            # before the multiply; this way it is the fp32 product rounded
+            # once, as in the bucket kernels
+            s = scale.to(p.grad.device)
+            p.grad.mul_(s if p.grad.dim() else s[0])
+        return scale
 
     # -- reducer binding ---------------------------------------------------
     def attach_reducer(self, reducer) -> None:
@@ -50,6 +171,10 @@ class FlatBucketOptimizer(torch.optim.Optimizer):
         self._bucketed = {id(p) for b in reducer.buckets for p in b.params}
         self._reducer = reducer
         self._bind_flat_state()
+        if self._max_grad_norm is not None and self._flat_pairs:
+            self._bind_clip_buffers(self._flat_pairs[0][0].device)
+        else:
+            self._clip_segments = None  # bound by the first clipped step
 
     def _stateful(self) -> bool:
         """Whether the configured update keeps per-parameter state."""

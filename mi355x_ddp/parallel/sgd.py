@@ -13,13 +13,17 @@ reference's torch.optim.SGD(lr=1e-3) (single_gpu.py:51).
   and models trained without the DDP engine).
 
 `state_dict()` interchanges with torch.optim.SGD over the same parameters
-(`momentum_buffer`, here always fp32). Limits: see flat_optim.py — single
-param_group when attached, host-scalar lr, no fp32 master weights for bf16.
+(`momentum_buffer`, here always fp32). `max_grad_norm` clips by the global
+L2 norm inside the step (flat_optim.py): the clip coefficient is folded into
+the same bucket kernels. Limits: see flat_optim.py — single param_group when
+attached, host-scalar lr, no fp32 master weights for bf16; clipping by the
+global L2 norm only (no other norm, no error_if_nonfinite), and
+`max_grad_norm` is not part of `state_dict()`.
 """
 
 from __future__ import annotations
 
-from typing import Iterable
+from typing import Iterable, Optional
 
 import torch
 
@@ -32,7 +36,8 @@ class FusedSGD(FlatBucketOptimizer):
 
     def __init__(self, params: Iterable[torch.nn.Parameter], lr: float,
                  momentum: float = 0, dampening: float = 0,
-                 weight_decay: float = 0, nesterov: bool = False):
+                 weight_decay: float = 0, nesterov: bool = False,
+                 max_grad_norm: Optional[float] = None):
         if lr <= 0:
             raise ValueError(f"invalid lr {lr}")
         if momentum < 0:
@@ -48,7 +53,8 @@ class FusedSGD(FlatBucketOptimizer):
         super().__init__(params, dict(lr=lr, momentum=momentum,
                                       dampening=dampening,
                                       weight_decay=weight_decay,
-                                      nesterov=nesterov))
+                                      nesterov=nesterov),
+                         max_grad_norm=max_grad_norm)
 
     def _stateful(self) -> bool:
         return any(g["momentum"] != 0 for g in self.param_groups)
@@ -67,6 +73,7 @@ class FusedSGD(FlatBucketOptimizer):
             with torch.enable_grad():
                 loss = closure()
         self._check_fenced()
+        scale = self._clip()  # loose grads are scaled in place there
         for group in self.param_groups:
             lr, mu = group["lr"], group["momentum"]
             wd, nesterov = group["weight_decay"], group["nesterov"]
@@ -75,7 +82,7 @@ class FusedSGD(FlatBucketOptimizer):
                 if self._flat_pairs is not None:
                     for flat_param, flat_grad in self._flat_pairs:
                         ops.sgd_flat_(flat_param, flat_grad, lr,
-                                      zero_grad=True)
+                                      zero_grad=True, grad_scale=scale)
                 for p in self._loose_params(group):
                     p.add_(p.grad, alpha=-lr)
                 continue
@@ -88,7 +95,7 @@ class FusedSGD(FlatBucketOptimizer):
                     ops.sgd_momentum_flat_(
                         flat_param, flat_grad,
                         bufs[bi] if mu != 0 else None, lr, mu, wd, nesterov,
-                        zero_grad=True)
+                        zero_grad=True, grad_scale=scale)
             for p in self._loose_params(group):
                 buf = self._param_state(p)["momentum_buffer"] \
                     if mu != 0 else None

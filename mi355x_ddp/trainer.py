@@ -184,7 +184,8 @@ class Trainer:
     def _try_fast_engine(self, kind: str) -> bool:
         """Engage the toy fast path when the configuration qualifies:
         HipLinear(K,1) model, MSE loss, plain FusedSGD (no momentum, no
-        weight decay — the toy kernels apply p -= lr*g and nothing else)
+        weight decay, no grad clipping — the toy kernels apply p -= lr*g
+        and nothing else)
         with a single lr, CUDA device. Returns False (caller keeps the
         hooks path) otherwise."""
         import torch.distributed as dist
@@ -197,6 +198,7 @@ class Trainer:
                 and self.loss_fn is ops.mse_loss
                 and isinstance(self.optimizer, FusedSGD)
                 and len(self.optimizer.param_groups) == 1
+                and getattr(self.optimizer, "max_grad_norm", None) is None
                 and self.optimizer.param_groups[0]["momentum"] == 0
                 and self.optimizer.param_groups[0]["weight_decay"] == 0):
             return False

@@ -19,6 +19,13 @@ the median time, beside the measured float4-copy rate of the chip
 (6.29 TB/s). fp32 momentum SGD reads p, g, buf and writes p, buf, g: 24 B
 per element; fp32 AdamW reads p, g, m, v and writes p, m, v, g: 32 B.
 
+The `+clip` configurations add clipping by the global L2 norm at 1.0:
+ours with max_grad_norm=1.0 (one k_sumsq_flat per bucket, one k_clip_coef,
+the coefficient folded into the update kernels), torch's as
+clip_grad_norm_(params, 1.0, foreach=True) ahead of the fused=True step
+and its zero_grad. Clipping MUST read g once more for the norm: 28 and
+36 B per element.
+
 Prints one JSON line (and writes it to --out when given). Needs a GPU.
 
 Usage: python tools/bench_optim.py [--iters 200] [--repeats 7] [--out F]
@@ -37,6 +44,8 @@ from mi355x_ddp.parallel import DDP, FusedAdamW, FusedSGD  # noqa: E402
 DEV = "cuda:0"
 COPY_RATE_TBS = 6.29  # measured float4 copy, MI355X_MICROARCH
 BYTES_PER_ELEM = {"sgd": 24, "adamw": 32}
+CLIP_EXTRA_BYTES = 4  # one more fp32 read of g, for the norm
+MAX_GRAD_NORM = 1.0
 
 
 class OneBucket(torch.nn.Module):
@@ -68,11 +77,15 @@ def build(workload, name):
     params = [p for p in model.parameters() if p.requires_grad]
     numel = sum(p.numel() for p in params)
     kind, impl = name.split("/")
+    clip = impl.endswith("+clip")
+    impl = impl[:-len("+clip")] if clip else impl
     if impl == "flat":
         eng = DDP(model, comm=None, bucket_cap_mb=1024.0
                   if workload == "bucket64MiB" else None)
-        opt = (FusedSGD(params, lr=1e-2, momentum=0.9, weight_decay=1e-4)
-               if kind == "sgd" else FusedAdamW(params))
+        kw = {"max_grad_norm": MAX_GRAD_NORM} if clip else {}
+        opt = (FusedSGD(params, lr=1e-2, momentum=0.9, weight_decay=1e-4,
+                        **kw)
+               if kind == "sgd" else FusedAdamW(params, **kw))
         opt.attach_reducer(eng.reducer)
         fill_grads(params)
         return opt.step, numel, len(eng.reducer.buckets), (model, eng, opt)
@@ -83,6 +96,9 @@ def build(workload, name):
     fill_grads(params)
 
     def step():
+        if clip:
+            torch.nn.utils.clip_grad_norm_(params, MAX_GRAD_NORM,
+                                           foreach=True)
         opt.step()
         opt.zero_grad(set_to_none=False)
 
@@ -126,7 +142,9 @@ def main():
         raise SystemExit("bench_optim.py measures on a GPU; none found")
 
     names = ["sgd/flat", "sgd/foreach", "sgd/fused",
-             "adamw/flat", "adamw/foreach", "adamw/fused"]
+             "sgd/flat+clip", "sgd/fused+clip",
+             "adamw/flat", "adamw/foreach", "adamw/fused",
+             "adamw/flat+clip", "adamw/fused+clip"]
     result = {"tool": "bench_optim", "device": torch.cuda.get_device_name(0),
               "iters": args.iters, "repeats": args.repeats,
               "copy_rate_TBs": COPY_RATE_TBS, "workloads": {}}
@@ -145,7 +163,9 @@ def main():
         for n in names:
             step, numel, buckets, _keep = cfgs[n]
             med = statistics.median(samples[n])
-            need = numel * BYTES_PER_ELEM[n.split("/")[0]]
+            need = numel * (BYTES_PER_ELEM[n.split("/")[0]]
+                            + (CLIP_EXTRA_BYTES if n.endswith("+clip")
+                               else 0))
             out[n] = {
                 "step_us_median": round(med, 2),
                 "step_us_min": round(min(samples[n]), 2),
@@ -167,6 +187,12 @@ def main():
             out[f"{kind}/flat_vs_torch_foreach"] = round(
                 out[f"{kind}/foreach"]["step_us_median"]
                 / ours["step_us_median"], 3)
+            clipped = out[f"{kind}/flat+clip"]
+            out[f"{kind}/flat+clip_vs_torch_fused+clip"] = round(
+                out[f"{kind}/fused+clip"]["step_us_median"]
+                / clipped["step_us_median"], 3)
+            out[f"{kind}/flat+clip_vs_flat"] = round(
+                clipped["step_us_median"] / ours["step_us_median"], 3)
         out["numel"] = cfgs[names[0]][1]
         result["workloads"][workload] = out
         del cfgs
