@@ -826,17 +826,25 @@ k_toy_multistep_bf16w(const __hip_bfloat16* __restrict__ X,
 struct RowPair {
   float lo, hi;
 };
-__device__ __forceinline__ RowPair bcast_rows01(float v) {
-  const unsigned u = __float_as_uint(v);
-  const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+// (v and v2 hold the same value: the swap works in place on two registers,
+// and a caller that makes the two copies itself decides where they stand.)
+__device__ __forceinline__ RowPair bcast_rows01(float v, float v2) {
+  const auto r = __builtin_amdgcn_permlane16_swap(
+      __float_as_uint(v), __float_as_uint(v2), false, false);
   return {__uint_as_float(r[0]), __uint_as_float(r[1])};
+}
+__device__ __forceinline__ RowPair bcast_rows01(float v) {
+  return bcast_rows01(v, v);
 }
 // Both half-waves of a per-lane value copied into both: lo = {r0, r1, r0,
 // r1}, hi = {r2, r3, r2, r3}.
-__device__ __forceinline__ RowPair bcast_halves(float v) {
-  const unsigned u = __float_as_uint(v);
-  const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+__device__ __forceinline__ RowPair bcast_halves(float v, float v2) {
+  const auto r = __builtin_amdgcn_permlane32_swap(
+      __float_as_uint(v), __float_as_uint(v2), false, false);
   return {__uint_as_float(r[0]), __uint_as_float(r[1])};
+}
+__device__ __forceinline__ RowPair bcast_halves(float v) {
+  return bcast_halves(v, v);
 }
 
 // acc = fmaf(src[lane n of the reader's row], x, acc): the same fused
@@ -846,7 +854,12 @@ __device__ __forceinline__ RowPair bcast_halves(float v) {
 // (update_dpp becomes v_mov_b32_dpp + v_fmac), hence asm; and one asm
 // statement per term gets an s_nop between every two, hence whole runs of
 // terms per statement (clang allows 30 operands). "+v" on the accumulator
-// keeps the statements in chain order.
+// keeps the statements in chain order, and `volatile` keeps them where
+// they stand among the step's other volatile statements and barriers: in
+// straight-line code the scheduler otherwise pulls the next step's settle,
+// barrier and fetch up between a step's forward and backward chains, into
+// fresh registers and with a wait right behind the reads. The forward
+// statement's memory clobber keeps the LDS reads issued ahead of it there.
 #define BC_DPP(n) " row_newbcast:" #n " row_mask:0xf bank_mask:0xf\n\t"
 #define BC_FMAC(src, x, n) \
   "v_fmac_f32_dpp %[acc], %[" #src "], %[" #x "]" BC_DPP(n)
@@ -865,28 +878,79 @@ __device__ __forceinline__ RowPair bcast_halves(float v) {
 // gfx9 wants 2 wait states between a VALU write of a VGPR and a DPP read
 // of it, and the hazard recogniser does not look inside asm: a statement
 // that may directly follow the swap that wrote its DPP source pads itself.
+// Every instruction of a lone wave costs an issue slot, an s_nop included
+// (profiles r07a), so a statement that starts a chain spends the first
+// wait state on zeroing its accumulator (BC_ZERO) instead of idling.
 #define BC_PAD "s_nop 1\n\t"
+#define BC_ZERO "v_mov_b32 %[acc], 0\n\ts_nop 0\n\t"
+
+// The recogniser also takes every VGPR an asm statement writes for a
+// dst_sel write, and puts a wait state in front of a VALU instruction that
+// reads one right behind the statement. So the plain instructions that
+// consume a chain's result stand inside its statement: the residual and
+// the loss gradient behind the forward chain, the parameter update behind
+// the last backward statement. They are the instructions the compiler
+// selects for the same expressions (v_sub_f32, v_mul_f32 by the constant,
+// and the one contracted v_fma_f32 of `w - lr * g`).
 
 // forward: y = sum_k w[k] * x[k] from +0 in k order (w[0..15] in row 0 =
-// w.lo, w[16..19] in row 1 = w.hi), then + bias (lane 20 = lane 4 of row 1)
-__device__ __forceinline__ float chain_fwd20(const RowPair& w,
-                                             const float (&x)[20]) {
-  float acc = 0.f;
-  asm(BC_PAD BC_FMAC16(lo, a) BC_FMAC4(hi, b, 0, 1, 2, 3)
-      "v_add_f32_dpp %[acc], %[hi], %[acc]" BC_DPP(4)
-      : [acc] "+v"(acc)
-      : [lo] "v"(w.lo), [hi] "v"(w.hi), BC_IN16(a, x), BC_IN4(b, x + 16));
-  return acc;
+// w.lo, w[16..19] in row 1 = w.hi), then + bias (lane 20 = lane 4 of row 1);
+// d = y - t, and with MSE dy = d * scale
+template <bool MSE>
+__device__ __forceinline__ void chain_fwd20(const RowPair& w,
+                                            const float (&x)[20], float t,
+                                            float scale, float& d,
+                                            float& dy) {
+  float acc;
+  if constexpr (MSE) {
+    asm volatile(BC_ZERO BC_FMAC16(lo, a) BC_FMAC4(hi, b, 0, 1, 2, 3)
+                 "v_add_f32_dpp %[acc], %[hi], %[acc]" BC_DPP(4)
+                 "v_sub_f32 %[d], %[acc], %[t]\n\t"
+                 "v_mul_f32 %[dy], %[c], %[d]"
+                 : [acc] "=&v"(acc), [d] "=&v"(d), [dy] "=&v"(dy)
+                 : [lo] "v"(w.lo), [hi] "v"(w.hi), BC_IN16(a, x),
+                   BC_IN4(b, x + 16), [t] "v"(t), [c] "s"(scale)
+                 : "memory");
+  } else {
+    asm volatile(BC_ZERO BC_FMAC16(lo, a) BC_FMAC4(hi, b, 0, 1, 2, 3)
+                 "v_add_f32_dpp %[acc], %[hi], %[acc]" BC_DPP(4)
+                 "v_sub_f32 %[d], %[acc], %[t]"
+                 : [acc] "=&v"(acc), [d] "=&v"(d)
+                 : [lo] "v"(w.lo), [hi] "v"(w.hi), BC_IN16(a, x),
+                   BC_IN4(b, x + 16), [t] "v"(t)
+                 : "memory");
+    dy = 0.f;
+  }
 }
-// backward: 16 terms acc += src[n] * x[n], n = 0..15 in order
-template <bool PAD>
+// backward: 16 terms acc += src[n] * x[n], n = 0..15 in order. kStart
+// begins the chain from +0 behind the swap that wrote src; kPad continues
+// a chain behind such a swap; kPlain continues it 16 terms later, and
+// chain_bwd16_update is kPlain followed by the update w = fma(-lr, acc, w).
+enum ChainLink { kStart, kPad, kPlain };
+template <ChainLink LINK>
 __device__ __forceinline__ void chain_bwd16(float& acc, float src,
                                             const float* x) {
-  if constexpr (PAD)
-    asm(BC_PAD BC_FMAC16(s, a) : [acc] "+v"(acc) : [s] "v"(src), BC_IN16(a, x));
+  if constexpr (LINK == kStart)
+    asm volatile(BC_ZERO BC_FMAC16(s, a)
+                 : [acc] "=&v"(acc)
+                 : [s] "v"(src), BC_IN16(a, x));
+  else if constexpr (LINK == kPad)
+    asm volatile(BC_PAD BC_FMAC16(s, a)
+                 : [acc] "+v"(acc)
+                 : [s] "v"(src), BC_IN16(a, x));
   else
-    asm(BC_FMAC16(s, a) : [acc] "+v"(acc) : [s] "v"(src), BC_IN16(a, x));
+    asm volatile(BC_FMAC16(s, a)
+                 : [acc] "+v"(acc)
+                 : [s] "v"(src), BC_IN16(a, x));
 }
+__device__ __forceinline__ void chain_bwd16_update(float& acc, float src,
+                                                   const float* x, float& w,
+                                                   float lr) {
+  asm volatile(BC_FMAC16(s, a) "v_fma_f32 %[w], -%[lr], %[acc], %[w]"
+               : [acc] "+v"(acc), [w] "+v"(w)
+               : [s] "v"(src), BC_IN16(a, x), [lr] "s"(lr));
+}
+#undef BC_ZERO
 #undef BC_PAD
 #undef BC_IN16
 #undef BC_IN4
@@ -1047,8 +1111,9 @@ k_toy_multistep_chain(const float* __restrict__ X,
   };
   LSet setA, setB;
 
-  auto fetch = [&](LSet& R, int slot) {
-    const int o = slot * L::kSize;
+  // o = the slot's dword offset in the ring; a constant one folds into the
+  // reads' immediate offsets
+  auto fetch = [&](LSet& R, int o) {
 #pragma unroll
     for (int j = 0; j < K_ / 4; ++j)
       R.xr[j] = *reinterpret_cast<const f32x4*>(rowp + o + 4 * j);
@@ -1087,8 +1152,18 @@ k_toy_multistep_chain(const float* __restrict__ X,
     float xc[B_];
     float t;
   };
+  // The forward swap's two copies of wv, made ahead of the step's fetch:
+  // the reads then stand in the wait states between the copies and the
+  // swap, where the compiler otherwise pads with an s_nop.
+  float wa, wb;
+  auto dup = [&] {
+    wa = wv, wb = wv;
+    asm volatile("" : "+v"(wa), "+v"(wb)::"memory");
+  };
   float d_last = 0.f;
-  auto compute = [&](const LSet& V) {
+  // mse = std::bool_constant of the launch's use_mse: the choice is made
+  // once around the step loops, not by a v_cndmask in every step
+  auto compute = [&](const LSet& V, auto mse) {
     CSet R;
 #pragma unroll
     for (int k = 0; k < K_; ++k) R.xr[k] = V.xr[k / 4][k % 4];
@@ -1098,32 +1173,30 @@ k_toy_multistep_chain(const float* __restrict__ X,
     // ---- forward: y = X @ w + b, k-ordered chain from +0 ----
     // rows 0/1 of wv reach every row that owns a batch row: rows 0..1 at
     // B_ = 32 (rows 2..3 run on copies of the bias, unused), all at 64
-    const RowPair w = bcast_rows01(B_ == 64 ? bcast_halves(wv).lo : wv);
-    const float y = chain_fwd20(w, R.xr);
-
-    // ---- loss grad: one row per lane ----
-    const float d = y - R.t;
-    const float dy = use_mse ? d * inv2B : 0.f;
+    RowPair w;
+    if constexpr (B_ == 64) w = bcast_rows01(bcast_halves(wa, wb).lo);
+    else w = bcast_rows01(wa, wb);
+    // ---- loss grad, one row per lane: d = y - t, dy = d * 2/B (or 0) ----
+    float d, dy;
+    chain_fwd20<decltype(mse)::value>(w, R.xr, R.t, inv2B, d, dy);
     d_last = d;
 
     // ---- backward: dw_k = sum_i dY_i X[i,k]; db on the ones lane ----
     // dy[i] lives in lane i; the chains live in rows 0..1. Only the first
     // reader of each swap's pair pads: the second runs 16 terms later.
-    float g = 0.f;
+    float g;
     if constexpr (B_ == 64) {
       const RowPair h = bcast_halves(dy);
       const RowPair p01 = bcast_rows01(h.lo), p23 = bcast_rows01(h.hi);
-      chain_bwd16<true>(g, p01.lo, R.xc);
-      chain_bwd16<false>(g, p01.hi, R.xc + 16);
-      chain_bwd16<true>(g, p23.lo, R.xc + 32);
-      chain_bwd16<false>(g, p23.hi, R.xc + 48);
+      chain_bwd16<kStart>(g, p01.lo, R.xc);
+      chain_bwd16<kPlain>(g, p01.hi, R.xc + 16);
+      chain_bwd16<kPad>(g, p23.lo, R.xc + 32);
+      chain_bwd16_update(g, p23.hi, R.xc + 48, wv, lr);
     } else {
       const RowPair p = bcast_rows01(dy);
-      chain_bwd16<true>(g, p.lo, R.xc);
-      chain_bwd16<false>(g, p.hi, R.xc + 16);
+      chain_bwd16<kStart>(g, p.lo, R.xc);
+      chain_bwd16_update(g, p.hi, R.xc + 16, wv, lr);
     }
-
-    wv = wv - lr * g;
     // compiler-only ordering point between steps
     __builtin_amdgcn_wave_barrier();
   };
@@ -1141,7 +1214,7 @@ k_toy_multistep_chain(const float* __restrict__ X,
         togo = H;
       }
       --togo;
-      fetch(R, slot);
+      fetch(R, slot * L::kSize);
       slot = (slot + 1 == slots) ? 0 : slot + 1;
     }
   };
@@ -1149,15 +1222,60 @@ k_toy_multistep_chain(const float* __restrict__ X,
   // odd steps through setB.
   asm volatile("" : "+v"(wv));  // the param load's wait, out of the loop
   fetch_step(setA, 0);
-  for (int s = 0; s < S; s += 2) {
-    settle(setA);
-    fetch_step(setB, s + 1);
-    compute(setA);  // step s
-    if (s + 1 < S) {
-      settle(setB);
-      fetch_step(setA, s + 2);
-      compute(setB);  // step s + 1
+  int s = 0;
+
+  // Whole turns of the ring, 2 HC steps with the depth a constant: the slot
+  // offsets are immediates of the reads and the two barriers stand at fixed
+  // places, so a step executes no bookkeeping and no branch at all. A turn
+  // starts and ends in the state fetch_step(setA, 0) leaves (step s in
+  // flight in setA from slot 0, slot = 1, togo = H - 1), runs only while
+  // each of its steps has a successor to fetch (s + 2 HC < S), and executes
+  // the barriers of the chunks it enters, exactly as the general loop
+  // below does; that loop takes over for the last 1 .. 2 HC steps.
+  auto turns = [&](auto hc) {
+    constexpr int HC = decltype(hc)::value;
+    for (; s + 2 * HC < S; s += 2 * HC) {
+#pragma unroll
+      for (int p = 0; p < HC; ++p) {
+        constexpr int kTurn = 2 * HC;
+        settle(setA);
+        if ((2 * p + 1) % HC == 0) __syncthreads();
+        dup();
+        fetch(setB, (2 * p + 1) * L::kSize);
+        compute(setA, std::true_type{});  // step s + 2 p
+        settle(setB);
+        if ((2 * p + 2) % HC == 0) __syncthreads();
+        dup();
+        fetch(setA, (2 * p + 2) % kTurn * L::kSize);
+        compute(setB, std::true_type{});  // step s + 2 p + 1
+      }
     }
+  };
+  auto steps = [&](auto mse) {
+    for (; s < S; s += 2) {
+      settle(setA);
+      dup();
+      fetch_step(setB, s + 1);
+      compute(setA, mse);  // step s
+      if (s + 1 < S) {
+        settle(setB);
+        dup();
+        fetch_step(setA, s + 2);
+        compute(setB, mse);  // step s + 1
+      }
+    }
+  };
+  if (use_mse) {
+    if (H == 2) turns(std::integral_constant<int, 2>{});
+    if constexpr (L::kMaxH >= 4) {
+      if (H == 3) turns(std::integral_constant<int, 3>{});
+      if (H == 4) turns(std::integral_constant<int, 4>{});
+    }
+    steps(std::true_type{});
+  } else {
+    // the degenerate cross-entropy path (dy = 0 whatever d is): general
+    // loop only
+    steps(std::false_type{});
   }
 
   if (lane < K_) param[w_off + lane] = wv;
@@ -1221,13 +1339,15 @@ void set_toy_multistep_chain_depth(int64_t depth) {
 
 // The chain depth is H, the steps per ring half (one barrier per H steps),
 // a runtime kernel argument clamped to what 64 KB of LDS holds (5 at batch
-// 32, 2 at batch 64). Measured at batch 32 (profiles r03d), H = 2 / 3 / 4:
-// S = 1024 -> 233 / 233 / 232 ns/step, S = 64 -> 267 / 270 / 273 (a launch
-// cannot start before its first H tiles are staged), so the default is the
-// smallest ring. One loader wave reaches the never-waiting ceiling at batch
-// 32; batch 64 gains 1.4% from a second one and nothing from a third.
+// 32, 2 at batch 64). Measured at batch 32 (profiles r07a), H = 2 / 3 / 4:
+// S = 1024 -> 177 / 174 / 175 ns/step, S = 64 -> 210 / 210 / 215 (a launch
+// cannot start before its first H tiles are staged), so the default stays
+// the smallest ring, which is all batch 64 can hold. With the compute
+// wave's step at 84 instructions one loader wave no longer keeps up at
+// batch 32 (231 ns/step against 177 with two); a third gains nothing at
+// either batch size.
 static constexpr int kChainDefaultH = 2;
-static constexpr int kChainLoaderWaves32 = 1;
+static constexpr int kChainLoaderWaves32 = 2;
 static constexpr int kChainLoaderWaves64 = 2;
 
 template <int B_>
