@@ -30,6 +30,21 @@ from .models.toy import HipLinear
 from .parallel.reducer import Reducer
 
 
+def _ramp_defaults():
+    """(ramp_first, growth) of the native stepper's launch ramp: the
+    measured choice (profiles/README.md r08), or MI355X_RAMP=FIRST:GROWTH
+    for A/B runs of bench.py (FIRST 0 = no ramp)."""
+    import os
+    env = os.environ.get("MI355X_RAMP")
+    if not env:
+        return 64, 1.5
+    first, growth = env.split(":")
+    return int(first), float(growth)
+
+
+RAMP_FIRST, RAMP_GROWTH = _ramp_defaults()
+
+
 # Process-wide capture poison: after ONE invalidated capture, any further
 # capture_begin in this process is lethal on this torch/ROCm build —
 # capture_begin raises "Cannot register the state during capturing stage"
@@ -163,10 +178,21 @@ class PersistentToyStep(ToyFusedStep):
     synchronizing the stream for timing/reading params — bench.py does
     before every barrier. Deferred-run length is capped by `max_defer`.
 
+    At world 1 the shard-bound protocol (`bind_shard` / `step_shard(i)` /
+    `flush`) is the extension's `ToyShardRun`: `step_shard` is a C function
+    and a launch is made from raw pointers. After a `flush()` — the caller
+    is about to synchronize, so the GPU will be idle — the first launches
+    are short and grow (`ramp_first` steps, then times `ramp_growth` per
+    launch up to `max_defer`; `ramp_first=0` for none), so the GPU starts
+    at once instead of waiting for the host to count `max_defer` steps.
+    An index outside the bound shard raises IndexError.
+
     With track_loss=True, loss_out holds the LAST executed step's loss.
     """
 
-    def __init__(self, *args, max_defer: int = 1024, **kwargs):
+    def __init__(self, *args, max_defer: int = 1024,
+                 ramp_first: int = RAMP_FIRST,
+                 ramp_growth: float = RAMP_GROWTH, **kwargs):
         super().__init__(*args, **kwargs)
         # world-1 (no comm), or a mesh-capable comm: the in-kernel xGMI
         # mesh exchange keeps SGD in-kernel at any world size
@@ -174,13 +200,28 @@ class PersistentToyStep(ToyFusedStep):
         assert self.comm is None or self._mesh is not None, \
             "PersistentToyStep needs world 1 or a P2pMeshComm"
         self.max_defer = max_defer
+        self.ramp_first = ramp_first
+        self.ramp_growth = ramp_growth
         self._install_fast_path()
+
+    @property
+    def launch_count(self) -> int:
+        """Kernel launches issued (bench transparency): the generic and
+        mesh paths' own plus the native stepper's."""
+        run = self._run
+        return self._launches + (run.launch_count if run is not None else 0)
 
     def _install_fast_path(self) -> None:
         """step/flush as closures over cell variables: the per-step cost is
-        two data_ptr() calls and a shape compare, no attribute traffic —
-        this loop runs a few hundred ns behind a kernel that takes ~1.3 us
-        per step, so host bookkeeping is the wall-clock bound."""
+        two data_ptr() calls and a shape compare, no attribute traffic.
+        The fp32 kernel takes under 200 ns per step, which is what a Python
+        closure call costs, so at world 1 the shard-bound protocol
+        (bind_shard/step_shard/flush, the path bench.py drives) does not
+        run here at all: it is the extension's ToyShardRun, whose
+        step_shard is a bare C function and whose launches ramp up after a
+        flush (docs/KERNELS.md, "The shard-bound stepper"). The mesh path
+        keeps the Python tracker below: every rank must issue the same
+        collectives in the same order, so its launch pattern stays fixed."""
         ext_mod = ops.ext() if ops.has_ext() else None
         flat_param = self.flat_param
         loss_out = self.loss_out
@@ -188,12 +229,17 @@ class PersistentToyStep(ToyFusedStep):
         lr, max_defer = self.lr, self.max_defer
         mesh = self._mesh
 
-        self.launch_count = 0  # kernel launches issued (bench transparency)
+        self._launches = 0
+        self._run = run = None
+        if mesh is None and ext_mod is not None and flat_param.is_cuda:
+            self._run = run = ext_mod.ToyShardRun(
+                flat_param, loss_out, use_mse, w_off, b_off, lr, max_defer,
+                self.ramp_first, self.ramp_growth)
 
         def launch(xall, tall, B):
             """One deferred-run launch: world-1 multistep, or the mesh
             variant with an in-kernel all-reduce per step."""
-            self.launch_count += 1
+            self._launches += 1
             if mesh is None:
                 ext_mod.toy_multistep(xall, tall, flat_param, loss_out,
                                       use_mse, w_off, b_off, lr, B)
@@ -214,7 +260,11 @@ class PersistentToyStep(ToyFusedStep):
 
         def step(x: torch.Tensor, t: torch.Tensor) -> None:
             nonlocal x0, t0, count, nx, nt, bk, bt, shape
-            if s_next != s_start:  # a shard-bound run is pending: order it
+            if run is not None:
+                if run.pending:  # a native shard-bound run: order it
+                    flush_generic()
+                    run.launch_pending()  # an internal flush: does not arm
+            elif s_next != s_start:  # a shard-bound run is pending: order it
                 flush()
             if count:
                 # fast path: the next contiguous slice of the pending run
@@ -224,23 +274,61 @@ class PersistentToyStep(ToyFusedStep):
                     nx += bk
                     nt += bt
                     if count >= max_defer:
-                        flush()
+                        flush_generic()
                     return
-                flush()
+                flush_generic()
             if not (x.is_cuda and x.is_contiguous() and t.is_contiguous()):
                 eager(x, t)
                 return
             x0, t0, count = x, t, 1
+            if run is not None:
+                # submitted before any later step_shard: the native run
+                # launches this one first (it cannot see it otherwise)
+                run.order_before(flush_generic)
             shape = x.shape
             bk = x.numel() * x.element_size()
             bt = t.numel() * t.element_size()
             nx = x.data_ptr() + bk
             nt = t.data_ptr() + bt
 
-        # shard-bound path: bind the epoch shard once, then step by batch
-        # INDEX — no per-step tensor-view construction at all. Used by
-        # bench.py's device-resident data path; step(x, t) remains the
-        # generic API.
+        def flush_generic() -> None:
+            nonlocal x0, t0, count
+            if count:
+                xx, tt, n = x0, t0, count
+                x0 = t0 = None
+                count = 0
+                if run is not None:
+                    run.order_before(None)
+                if n == 1:
+                    launch(xx, tt, xx.shape[0])  # S=1: bitwise == fused
+                else:
+                    B, K = xx.shape
+                    xall = xx.as_strided((n * B, K), (K, 1))
+                    tall = tt.as_strided((n * B,) + tt.shape[1:],
+                                         (tt.stride(0),) + tt.stride()[1:])
+                    launch(xall, tall, B)
+
+        self.step = step
+        if run is not None:
+            # a tensor-level run still pending was submitted first: it goes
+            # first here, as it does (order_before) ahead of a native launch
+            def flush() -> None:
+                flush_generic()
+                run.flush()  # launches what is pending and arms the ramp
+
+            def bind_shard(xs: torch.Tensor, ts: torch.Tensor,
+                           batch: int) -> None:
+                flush_generic()
+                run.bind_shard(xs, ts, batch)
+
+            self.flush = flush
+            self.bind_shard = bind_shard
+            self.step_shard = run.step_shard  # the C function itself
+            return
+
+        # shard-bound path in Python (mesh, or no extension): bind the
+        # epoch shard once, then step by batch INDEX — no per-step
+        # tensor-view construction at all.
         shard_x = shard_t = None
         sbatch = 0
         s_start = s_next = 0  # pending run = batch indices [s_start, s_next)
@@ -263,25 +351,13 @@ class PersistentToyStep(ToyFusedStep):
             s_start, s_next = i, i + 1
 
         def flush() -> None:
-            nonlocal x0, t0, count, s_start, s_next
-            if count:
-                xx, tt, n = x0, t0, count
-                x0 = t0 = None
-                count = 0
-                if n == 1:
-                    launch(xx, tt, xx.shape[0])  # S=1: bitwise == fused
-                else:
-                    B, K = xx.shape
-                    xall = xx.as_strided((n * B, K), (K, 1))
-                    tall = tt.as_strided((n * B,) + tt.shape[1:],
-                                         (tt.stride(0),) + tt.stride()[1:])
-                    launch(xall, tall, B)
+            nonlocal s_start, s_next
+            flush_generic()
             if s_next > s_start:
                 lo, n = s_start * sbatch, (s_next - s_start) * sbatch
                 s_start = s_next
                 launch(shard_x[lo:lo + n], shard_t[lo:lo + n], sbatch)
 
-        self.step = step
         self.flush = flush
         self.bind_shard = bind_shard
         self.step_shard = step_shard

@@ -1,10 +1,16 @@
 // Python bindings for the mi355x_ddp native layer (kernels + RCCL comm).
 #include <torch/extension.h>
 
+#include <functional>
+#include <memory>
+#include <utility>
+#include <vector>
+
 #include "ops.h"
 #include "p2p_mesh.h"
 #include "rccl_comm.h"
 #include "reducer_core.h"
+#include "shard_run.h"
 
 namespace mi355x {
 // autograd_ops.hip
@@ -12,6 +18,193 @@ torch::Tensor linear_autograd(torch::Tensor x, torch::Tensor w,
                               c10::optional<torch::Tensor> b);
 torch::Tensor mse_autograd(torch::Tensor y, torch::Tensor t);
 torch::Tensor ce_autograd(torch::Tensor y, torch::Tensor t);
+
+// The native shard-bound stepper of the world-1 persistent engine: the
+// shard_run.h tracker over toy_multistep_launch. bind_shard validates the
+// shard once and keeps raw pointers; step_shard(i) is then a few integer
+// operations, and a launch is pointer arithmetic plus the kernel dispatch.
+// The recorder variant has the same tracker and entry point but only notes
+// (first_step, n_steps) and touches no GPU API, so the schedule and the
+// host-loop cost are testable without a GPU.
+class ToyShardRun : public std::enable_shared_from_this<ToyShardRun> {
+ public:
+  using Tracker = ShardRun<std::function<void(int64_t, int64_t)>>;
+
+  ToyShardRun(torch::Tensor flat_param, torch::Tensor loss_out, bool use_mse,
+              int64_t w_off, int64_t b_off, double lr, int64_t max_defer,
+              int64_t ramp_first, double growth)
+      : param_(std::move(flat_param)), loss_(std::move(loss_out)),
+        use_mse_(use_mse), w_off_((int)w_off), b_off_((int)b_off),
+        lr_((float)lr),
+        run_([this](int64_t first, int64_t n) { launch(first, n); },
+             max_defer, ramp_first, growth) {
+    TORCH_CHECK(param_.is_cuda() && param_.is_contiguous(),
+                "ToyShardRun: flat_param must be a contiguous device tensor");
+    const auto dt = param_.scalar_type();
+    TORCH_CHECK(dt == at::kFloat || dt == at::kBFloat16,
+                "ToyShardRun: flat_param must be f32 or bf16, got ", dt);
+    bf16_ = dt == at::kBFloat16;
+    TORCH_CHECK(lr > 0.0, "ToyShardRun applies SGD in-kernel: lr must be > 0");
+    TORCH_CHECK(w_off >= 0 && b_off >= 0 && b_off < param_.numel() &&
+                    w_off < param_.numel(),
+                "ToyShardRun: w_off/b_off outside flat_param");
+    lossp_ = toy_loss_ptr(loss_);
+    TORCH_CHECK(lossp_ == nullptr || (loss_.is_cuda() &&
+                                      loss_.device() == param_.device()),
+                "ToyShardRun: loss_out must be on flat_param's device");
+  }
+
+  // recorder
+  ToyShardRun(int64_t steps_bound, int64_t max_defer, int64_t ramp_first,
+              double growth)
+      : recorder_(true),
+        run_([this](int64_t first, int64_t n) {
+               recorded_.emplace_back(first, n);
+             },
+             max_defer, ramp_first, growth) {
+    run_.bind(steps_bound);
+  }
+
+  ToyShardRun(const ToyShardRun&) = delete;
+  ToyShardRun& operator=(const ToyShardRun&) = delete;
+
+  void bind_shard(torch::Tensor xs, torch::Tensor ts, int64_t batch) {
+    TORCH_CHECK(!recorder_, "a recorder binds step counts: use bind_steps");
+    TORCH_CHECK(xs.is_cuda() && ts.is_cuda() &&
+                    xs.device() == param_.device() &&
+                    ts.device() == param_.device(),
+                "bind_shard: xs/ts must be on flat_param's device");
+    TORCH_CHECK(xs.dim() == 2 && xs.is_contiguous() && ts.is_contiguous(),
+                "bind_shard: xs must be [rows, K], xs/ts contiguous");
+    TORCH_CHECK(xs.scalar_type() == param_.scalar_type() &&
+                    ts.scalar_type() == param_.scalar_type(),
+                "bind_shard: xs/ts dtype must match flat_param");
+    TORCH_CHECK(ts.dim() >= 1 && ts.size(0) == xs.size(0) &&
+                    ts.numel() == ts.size(0),
+                "bind_shard: ts must hold one target per row of xs");
+    const int64_t K = xs.size(1);
+    TORCH_CHECK(batch >= 1 && batch <= 128 && K >= 1 && K <= 32,
+                "toy multistep supports B<=128, K<=32");
+    TORCH_CHECK(xs.size(0) % batch == 0,
+                "bind_shard: rows must be a multiple of batch");
+    TORCH_CHECK(w_off_ + K <= param_.numel(),
+                "bind_shard: K weights do not fit flat_param at w_off");
+    run_.launch_pending();  // what is pending runs on the OLD shard
+    xs_ = std::move(xs);
+    ts_ = std::move(ts);
+    B_ = (int)batch;
+    K_ = (int)K;
+    run_.bind(xs_.size(0) / batch);
+  }
+
+  void bind_steps(int64_t steps_bound) {
+    TORCH_CHECK(recorder_, "bind_steps is the recorder's bind");
+    run_.bind(steps_bound);
+  }
+
+  // The engine's tensor-level step(x, t) path defers runs of its own. One
+  // still pending when this run launches was submitted FIRST, so it has to
+  // be launched first: `cb` (None clears) is called once, before the next
+  // launch from here.
+  void order_before(pybind11::object cb) {
+    before_launch_ = cb.is_none() ? pybind11::object() : std::move(cb);
+  }
+
+  Tracker& tracker() { return run_; }
+  const std::vector<std::pair<int64_t, int64_t>>& recorded() const {
+    return recorded_;
+  }
+
+ private:
+  void launch(int64_t first, int64_t n) {
+    // [first, first + n) lies inside the bound rows: step() admits no index
+    // at or past rows / batch
+    if (before_launch_) {
+      pybind11::object cb = std::move(before_launch_);
+      before_launch_ = pybind11::object();
+      cb();
+    }
+    const int64_t esz = bf16_ ? 2 : 4;
+    const char* xp = static_cast<const char*>(xs_.data_ptr());
+    const char* tp = static_cast<const char*>(ts_.data_ptr());
+    toy_multistep_launch(xp + first * B_ * K_ * esz, tp + first * B_ * esz,
+                         param_.data_ptr(), lossp_, use_mse_, w_off_, b_off_,
+                         lr_, B_, K_, (int)n, bf16_);
+  }
+
+  torch::Tensor param_, loss_, xs_, ts_;
+  float* lossp_ = nullptr;
+  bool use_mse_ = true, bf16_ = false, recorder_ = false;
+  int w_off_ = 0, b_off_ = 0, B_ = 0, K_ = 0;
+  float lr_ = 0.f;
+  std::vector<std::pair<int64_t, int64_t>> recorded_;
+  pybind11::object before_launch_;
+  Tracker run_;  // last: its launch callable uses the members above
+};
+
+// step_shard as a bare METH_O C function whose self is a capsule owning a
+// shared_ptr to the run: the per-step call pays neither pybind11's
+// dispatcher nor a Python frame. No pybind translation here, so C++
+// exceptions are turned into Python ones by hand.
+static const char* const kRunCapsule = "mi355x_ddp._C.ToyShardRun";
+
+static PyObject* shard_run_step_slow(ToyShardRun& run, PyObject* arg);
+
+static PyObject* shard_run_step(PyObject* self, PyObject* arg) {
+  auto* sp = static_cast<std::shared_ptr<ToyShardRun>*>(
+      PyCapsule_GetPointer(self, kRunCapsule));
+  if (sp == nullptr) return nullptr;
+  // all but one step in a threshold's worth only extend the pending run:
+  // that needs no exception handling at all
+  if (PyLong_Check(arg)) {
+    int overflow = 0;
+    const long long i = PyLong_AsLongLongAndOverflow(arg, &overflow);
+    if (!overflow && (*sp)->tracker().extend(i)) Py_RETURN_NONE;
+  }
+  return shard_run_step_slow(**sp, arg);
+}
+
+static PyObject* shard_run_step_slow(ToyShardRun& run, PyObject* arg) {
+  HANDLE_TH_ERRORS
+  if (!PyLong_Check(arg)) {
+    PyErr_Format(PyExc_TypeError,
+                 "step_shard() takes an int batch index, not %.200s",
+                 Py_TYPE(arg)->tp_name);
+    return nullptr;
+  }
+  int overflow = 0;
+  const long long i = PyLong_AsLongLongAndOverflow(arg, &overflow);
+  if (i == -1 && PyErr_Occurred()) return nullptr;
+  try {
+    if (overflow) throw std::out_of_range("step index does not fit 64 bits");
+    run.tracker().step(i);
+  } catch (const std::out_of_range& e) {
+    PyErr_SetString(PyExc_IndexError, e.what());
+    return nullptr;
+  }
+  Py_RETURN_NONE;
+  END_HANDLE_TH_ERRORS
+}
+
+static PyMethodDef kShardRunStepDef = {
+    "step_shard", shard_run_step, METH_O,
+    "step_shard(i): run step i of the bound shard (deferred; see flush)"};
+
+static pybind11::object shard_run_step_fn(ToyShardRun& run) {
+  auto* sp = new std::shared_ptr<ToyShardRun>(run.shared_from_this());
+  PyObject* cap = PyCapsule_New(sp, kRunCapsule, [](PyObject* c) {
+    delete static_cast<std::shared_ptr<ToyShardRun>*>(
+        PyCapsule_GetPointer(c, kRunCapsule));
+  });
+  if (cap == nullptr) {
+    delete sp;
+    throw pybind11::error_already_set();
+  }
+  PyObject* fn = PyCFunction_New(&kShardRunStepDef, cap);
+  Py_DECREF(cap);  // the function object owns it now
+  if (fn == nullptr) throw pybind11::error_already_set();
+  return pybind11::reinterpret_steal<pybind11::object>(fn);
+}
 }  // namespace mi355x
 
 namespace py = pybind11;
@@ -91,6 +284,51 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("get_toy_multistep_impl", &mi355x::get_toy_multistep_impl);
   m.def("set_toy_multistep_chain_depth",
         &mi355x::set_toy_multistep_chain_depth, py::arg("depth"));
+
+  // Native shard-bound stepper (world-1 persistent engine). step_shard is a
+  // bare C function, fetched once and called per step; the rest is cold.
+  py::class_<mi355x::ToyShardRun, std::shared_ptr<mi355x::ToyShardRun>>(
+      m, "ToyShardRun")
+      .def(py::init<torch::Tensor, torch::Tensor, bool, int64_t, int64_t,
+                    double, int64_t, int64_t, double>(),
+           py::arg("flat_param"), py::arg("loss_out"), py::arg("use_mse"),
+           py::arg("w_off"), py::arg("b_off"), py::arg("lr"),
+           py::arg("max_defer"), py::arg("ramp_first"), py::arg("growth"))
+      .def_static("recorder",
+                  [](int64_t steps_bound, int64_t max_defer,
+                     int64_t ramp_first, double growth) {
+                    return std::make_shared<mi355x::ToyShardRun>(
+                        steps_bound, max_defer, ramp_first, growth);
+                  },
+                  py::arg("steps_bound"), py::arg("max_defer"),
+                  py::arg("ramp_first"), py::arg("growth"))
+      .def("bind_shard", &mi355x::ToyShardRun::bind_shard, py::arg("xs"),
+           py::arg("ts"), py::arg("batch"))
+      .def("bind_steps", &mi355x::ToyShardRun::bind_steps,
+           py::arg("steps_bound"))
+      .def("order_before", &mi355x::ToyShardRun::order_before, py::arg("cb"))
+      .def("flush", [](mi355x::ToyShardRun& r) { r.tracker().flush(); })
+      .def("launch_pending",
+           [](mi355x::ToyShardRun& r) { r.tracker().launch_pending(); })
+      .def_property_readonly("step_shard", &mi355x::shard_run_step_fn)
+      .def_property_readonly(
+          "launch_count",
+          [](mi355x::ToyShardRun& r) { return r.tracker().launch_count(); })
+      .def_property_readonly(
+          "max_defer",
+          [](mi355x::ToyShardRun& r) { return r.tracker().max_defer(); })
+      .def_property_readonly(
+          "pending",
+          [](mi355x::ToyShardRun& r) { return r.tracker().pending(); })
+      .def_property_readonly(
+          "threshold",
+          [](mi355x::ToyShardRun& r) { return r.tracker().threshold(); })
+      .def_property_readonly("launches", [](mi355x::ToyShardRun& r) {
+        py::list out;
+        for (const auto& l : r.recorded())
+          out.append(py::make_tuple(l.first, l.second));
+        return out;
+      });
 
   py::class_<mi355x::P2pMesh>(m, "P2pMesh")
       .def(py::init<int, int, int>(), py::arg("rank"), py::arg("world"),

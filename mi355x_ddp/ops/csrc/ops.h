@@ -146,6 +146,20 @@ void toy_multistep(torch::Tensor x, torch::Tensor t, torch::Tensor param_flat,
                    torch::Tensor loss_out, bool use_mse,
                    int64_t w_off, int64_t b_off, double lr, int64_t batch);
 
+// The launcher under toy_multistep, on raw device pointers: x/t point at the
+// first of S consecutive [B, K] / [B] tiles of storage dtype f32 or bf16
+// (param has the same dtype, loss is f32 or null). It does toy_multistep's
+// kernel dispatch, reading the selector and the ring depth below at launch
+// time, launches on the current stream and checks hipGetLastError. The
+// caller has validated shapes, dtypes and devices: B <= 128, K <= 32,
+// S >= 1, lr > 0. The native stepper (ToyShardRun, bindings.hip) validates
+// once per bind and then launches through this.
+void toy_multistep_launch(const void* x, const void* t, void* param,
+                          float* loss, bool use_mse, int w_off, int b_off,
+                          float lr, int B, int K, int S, bool bf16);
+// Validated pointer of the optional f32 loss output (nullptr when empty).
+float* toy_loss_ptr(const torch::Tensor& loss_out);
+
 // Process-wide kernel selector for the fp32 batch-32/64, K-20 multi-step
 // fast path: "chain" (lane-parallel fmaf chains on the vector ALU, the
 // default) or "mfma" (k_toy_multistep_spec). Both produce the same bits.

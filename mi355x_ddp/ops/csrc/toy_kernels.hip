@@ -1430,13 +1430,9 @@ static int multistep_steps(const torch::Tensor& x, const torch::Tensor& t,
 }
 
 template <typename T>
-static void launch_toy_multistep(const torch::Tensor& x, const torch::Tensor& t,
-                                 torch::Tensor& param_flat, float* lossp,
+static void launch_toy_multistep(const T* xp, const T* tp, T* pp, float* lossp,
                                  bool use_mse, int w_off, int b_off, float lr,
                                  int B, int K, int S) {
-  const T* xp = cdptr<T>(x);
-  const T* tp = cdptr<T>(t);
-  T* pp = dptr<T>(param_flat);
   if ((B == 32 || B == 64) && K == 20) {  // compile-time fast paths
     with_fast_batch(B, [&](auto b) {
       constexpr int B_ = decltype(b)::value;
@@ -1459,6 +1455,25 @@ static void launch_toy_multistep(const torch::Tensor& x, const torch::Tensor& t,
   });
 }
 
+void toy_multistep_launch(const void* x, const void* t, void* param,
+                          float* loss, bool use_mse, int w_off, int b_off,
+                          float lr, int B, int K, int S, bool bf16) {
+  if (bf16) {
+    using T = __hip_bfloat16;
+    launch_toy_multistep<T>(static_cast<const T*>(x), static_cast<const T*>(t),
+                            static_cast<T*>(param), loss, use_mse, w_off,
+                            b_off, lr, B, K, S);
+  } else {
+    launch_toy_multistep<float>(static_cast<const float*>(x),
+                                static_cast<const float*>(t),
+                                static_cast<float*>(param), loss, use_mse,
+                                w_off, b_off, lr, B, K, S);
+  }
+  HIP_OK(hipGetLastError());
+}
+
+float* toy_loss_ptr(const torch::Tensor& loss_out) { return loss_ptr(loss_out); }
+
 void toy_multistep(torch::Tensor x, torch::Tensor t, torch::Tensor param_flat,
                    torch::Tensor loss_out, bool use_mse,
                    int64_t w_off, int64_t b_off, double lr, int64_t batch) {
@@ -1468,11 +1483,12 @@ void toy_multistep(torch::Tensor x, torch::Tensor t, torch::Tensor param_flat,
       x, t, B, lr, "toy_multistep is the world-1 in-kernel-SGD path");
   if (S == 0) return;
   float* lossp = loss_ptr(loss_out);
-  DISPATCH_F32_BF16(x.scalar_type(), "toy_multistep", {
-    launch_toy_multistep<scalar_t>(x, t, param_flat, lossp, use_mse,
-                                   (int)w_off, (int)b_off, (float)lr, B, K, S);
-  });
-  HIP_OK(hipGetLastError());
+  const auto dt = x.scalar_type();
+  TORCH_CHECK(dt == at::kFloat || dt == at::kBFloat16,
+              "toy_multistep: unsupported dtype ", dt);
+  toy_multistep_launch(x.data_ptr(), t.data_ptr(), param_flat.data_ptr(),
+                       lossp, use_mse, (int)w_off, (int)b_off, (float)lr, B,
+                       K, S, dt == at::kBFloat16);
 }
 
 void toy_multistep_mesh(torch::Tensor x, torch::Tensor t,
