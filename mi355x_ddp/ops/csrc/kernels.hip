@@ -113,7 +113,8 @@ template <bool B_T>
 static torch::Tensor linear_tile(const torch::Tensor& a, const torch::Tensor& w,
                                  const c10::optional<torch::Tensor>& bias,
                                  const char* name) {
-  TORCH_CHECK(a.is_cuda() && w.is_cuda(), name, ": operands must be on device");
+  TORCH_CHECK(a.is_cuda() && w.device() == a.device(), name,
+              ": operands must be on one device");
   TORCH_CHECK(a.dim() == 2 && w.dim() == 2 &&
                   a.size(1) == w.size(B_T ? 1 : 0),
               name, ": shape mismatch");
@@ -122,9 +123,17 @@ static torch::Tensor linear_tile(const torch::Tensor& a, const torch::Tensor& w,
   auto wc = w.contiguous();
   const int M = (int)ac.size(0), Kc = (int)ac.size(1);
   const int Nc = (int)wc.size(B_T ? 0 : 1);
-  auto c = at::empty({M, Nc}, a.options());
   torch::Tensor bc;
-  if (bias.has_value()) bc = bias->contiguous();
+  if (bias.has_value()) {
+    TORCH_CHECK(bias->device() == a.device() &&
+                    bias->scalar_type() == a.scalar_type() &&
+                    bias->dim() == 1 && bias->size(0) == Nc,
+                name, ": bias must be a [", Nc, "] tensor of the operands' ",
+                "dtype and device");
+    bc = bias->contiguous();
+  }
+  auto c = at::empty({M, Nc}, a.options());
+  if (M == 0 || Nc == 0) return c;  // nothing to compute: no zero-block grid
   const bool split = M < 64;
   const dim3 grid(cdiv(M, split ? 16 : 64), cdiv(Nc, 16));
   DISPATCH_F32_BF16(a.scalar_type(), name, {
@@ -201,10 +210,35 @@ __global__ void k_linear_bwd_w(const T* __restrict__ X,
 
 void linear_bwd_weight(torch::Tensor x, torch::Tensor dy,
                        torch::Tensor dw, torch::Tensor db, bool accumulate) {
+  const char* name = "linear_bwd_weight";
+  TORCH_CHECK(x.is_cuda() && dy.device() == x.device() &&
+                  dw.device() == x.device() && db.device() == x.device(),
+              name, ": x, dy, dw and db must be on one device");
+  TORCH_CHECK(dy.scalar_type() == x.scalar_type() &&
+                  dw.scalar_type() == x.scalar_type() &&
+                  db.scalar_type() == x.scalar_type(),
+              name, ": dtype mismatch (x ", x.scalar_type(), ", dy ",
+              dy.scalar_type(), ", dw ", dw.scalar_type(), ", db ",
+              db.scalar_type(), ")");
+  TORCH_CHECK(x.dim() == 2 && dy.dim() == 2 && dy.size(0) == x.size(0), name,
+              ": shape mismatch, x must be [B,K] and dy [B,N]");
+  TORCH_CHECK(dw.dim() == 2 && dw.size(0) == dy.size(1) &&
+                  dw.size(1) == x.size(1),
+              name, ": dw must be [N,K] = [", dy.size(1), ",", x.size(1), "]");
+  // an empty db means: no bias gradient wanted
+  TORCH_CHECK(db.numel() == 0 || (db.dim() == 1 && db.size(0) == dy.size(1)),
+              name, ": db must be empty or [N] = [", dy.size(1), "]");
   auto xc = x.contiguous();
   auto dyc = dy.contiguous();
   TORCH_CHECK(dw.is_contiguous() && db.is_contiguous(), "grad views must be contiguous");
   const int B = (int)xc.size(0), K = (int)xc.size(1), N = (int)dyc.size(1);
+  if (B == 0 || K == 0 || N == 0) {  // an empty contraction or an empty dW
+    if (!accumulate) {
+      dw.zero_();
+      db.zero_();
+    }
+    return;
+  }
   dim3 grid(cdiv(K, 64), cdiv(N, 16));
   DISPATCH_F32_BF16(x.scalar_type(), "linear_bwd_weight", {
     hipLaunchKernelGGL((k_linear_bwd_w<scalar_t>), grid, dim3(256), 0,
@@ -268,14 +302,26 @@ __global__ void k_gemm_bf16(const __hip_bfloat16* __restrict__ X,
 
 torch::Tensor gemm_bf16(torch::Tensor x, torch::Tensor w,
                         c10::optional<torch::Tensor> bias) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16);
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16,
+              "gemm_bf16: x must be a device bf16 tensor");
+  TORCH_CHECK(w.device() == x.device() && w.scalar_type() == at::kBFloat16,
+              "gemm_bf16: w must be bf16 on x's device");
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.size(1) == w.size(1),
+              "gemm_bf16: shape mismatch, x must be [B,K] and w [N,K]");
   auto xc = x.contiguous();
   auto wc = w.contiguous();
   const int B = (int)xc.size(0), K = (int)xc.size(1), N = (int)wc.size(0);
-  auto y = at::empty({B, N}, x.options());
   torch::Tensor bc;
   bool has_bias = bias.has_value();
-  if (has_bias) bc = bias->contiguous();
+  if (has_bias) {
+    TORCH_CHECK(bias->device() == x.device() &&
+                    bias->scalar_type() == at::kBFloat16 &&
+                    bias->dim() == 1 && bias->size(0) == N,
+                "gemm_bf16: bias must be a bf16 [", N, "] tensor on x's device");
+    bc = bias->contiguous();
+  }
+  auto y = at::empty({B, N}, x.options());
+  if (B == 0 || N == 0) return y;
   dim3 grid(cdiv(B, 64), cdiv(N, 16));
   hipLaunchKernelGGL(k_gemm_bf16, grid, dim3(256), 0, cur_stream(),
                      cdptr<__hip_bfloat16>(xc), cdptr<__hip_bfloat16>(wc),
@@ -311,19 +357,26 @@ __global__ void k_ce_fwd(const T* __restrict__ Y, const T* __restrict__ Tg,
     const float tv = ldf(&t[c]);
     se += __expf(yv - m);
     ts += tv;
-    ty += tv * yv;
+    ty += tv * (yv - m);
   }
   se = wave_sum(se); ts = wave_sum(ts); ty = wave_sum(ty);
   const float inv_se = 1.f / se;
   for (int c = lane; c < C; c += 64) p[c] = __expf(ldf(&y[c]) - m) * inv_se;
   if (lane == 0) {
     tsum[row] = ts;
-    const float logZ = m + __logf(se);
-    atomicAdd(loss, (ts * logZ - ty) / (float)B);
+    // -sum_c t_c * log_softmax(y)_c with the row max taken out of BOTH
+    // terms: ts * (m + log se) - sum t*y cancels catastrophically once the
+    // logits share a large offset (an f32 ulp at 1e4 is 1e-3)
+    atomicAdd(loss, (ts * __logf(se) - ty) / (float)B);
   }
 }
 
 std::vector<torch::Tensor> ce_fwd(torch::Tensor y, torch::Tensor t) {
+  TORCH_CHECK(y.is_cuda() && t.device() == y.device(),
+              "ce_fwd: output and targets must be on one device");
+  TORCH_CHECK(y.dim() == 2, "ce_fwd: the output must be [B,C]");
+  TORCH_CHECK(t.scalar_type() == y.scalar_type(), "ce_fwd: dtype mismatch (",
+              y.scalar_type(), " output, ", t.scalar_type(), " targets)");
   auto yc = y.contiguous();
   auto tc = t.contiguous();
   TORCH_CHECK(tc.sizes() == yc.sizes(),
@@ -331,6 +384,10 @@ std::vector<torch::Tensor> ce_fwd(torch::Tensor y, torch::Tensor t) {
               tc.sizes(), " vs ", yc.sizes(), ")");
   const int B = (int)yc.size(0), C = (int)yc.size(1);
   auto f32opt = yc.options().dtype(at::kFloat);
+  if (B == 0 || C == 0) {  // torch: the mean over nothing is nan
+    return {at::full({}, NAN, f32opt), at::empty({B, C}, f32opt),
+            at::zeros({B}, f32opt)};
+  }
   auto probs = at::empty({B, C}, f32opt);
   auto tsum = at::empty({B}, f32opt);
   auto loss = at::zeros({}, f32opt);
@@ -375,11 +432,24 @@ __global__ void k_ce_bwd(const float* __restrict__ P, const T* __restrict__ Tg,
 torch::Tensor ce_bwd(torch::Tensor probs, torch::Tensor t,
                      torch::Tensor tsum, double grad_scale,
                      c10::optional<torch::Tensor> gout) {
+  TORCH_CHECK(t.is_cuda() && probs.device() == t.device() &&
+                  tsum.device() == t.device(),
+              "ce_bwd: probs, targets and tsum must be on one device");
+  TORCH_CHECK(probs.scalar_type() == at::kFloat &&
+                  tsum.scalar_type() == at::kFloat,
+              "ce_bwd: probs and tsum are the f32 outputs of ce_fwd");
+  TORCH_CHECK(probs.dim() == 2 && probs.is_contiguous() &&
+                  t.sizes() == probs.sizes(),
+              "ce_bwd: probs must be contiguous [B,C] and match the targets");
+  TORCH_CHECK(tsum.dim() == 1 && tsum.size(0) == probs.size(0) &&
+                  tsum.is_contiguous(),
+              "ce_bwd: tsum must be contiguous [B]");
   const int B = (int)probs.size(0), C = (int)probs.size(1);
   auto tc = t.contiguous();
   auto dy = at::empty({B, C}, tc.options());
   const int64_t n = (int64_t)B * C;
   const float* gp = gout_ptr(gout, "ce_bwd");
+  if (n == 0) return dy;
   DISPATCH_F32_BF16(tc.scalar_type(), "ce_bwd", {
     hipLaunchKernelGGL((k_ce_bwd<scalar_t>), dim3(cdiv(n, 256)), dim3(256), 0,
                        cur_stream(), probs.data_ptr<float>(),
@@ -425,7 +495,13 @@ torch::Tensor mse_fwd(torch::Tensor y, torch::Tensor t) {
   // hard error is safe.
   TORCH_CHECK(tc.sizes() == yc.sizes(), "mse: target shape ", tc.sizes(),
               " != output shape ", yc.sizes());
+  TORCH_CHECK(y.is_cuda() && t.device() == y.device(),
+              "mse_fwd: output and target must be on one device");
+  TORCH_CHECK(t.scalar_type() == y.scalar_type(), "mse_fwd: dtype mismatch (",
+              y.scalar_type(), " output, ", t.scalar_type(), " target)");
   const int64_t n = yc.numel();
+  if (n == 0)  // torch: the mean over nothing is nan
+    return at::full({}, NAN, yc.options().dtype(at::kFloat));
   auto loss = at::zeros({}, yc.options().dtype(at::kFloat));
   const int blocks = (int)std::min<int64_t>(cdiv(n, 256), 2048);
   DISPATCH_F32_BF16(y.scalar_type(), "mse_fwd", {
@@ -448,11 +524,18 @@ __global__ void k_mse_bwd(const T* __restrict__ Y, const T* __restrict__ Tg,
 
 torch::Tensor mse_bwd(torch::Tensor y, torch::Tensor t, double grad_scale,
                       c10::optional<torch::Tensor> gout) {
+  TORCH_CHECK(y.is_cuda() && t.device() == y.device(),
+              "mse_bwd: output and target must be on one device");
+  TORCH_CHECK(t.scalar_type() == y.scalar_type(), "mse_bwd: dtype mismatch (",
+              y.scalar_type(), " output, ", t.scalar_type(), " target)");
+  TORCH_CHECK(t.sizes() == y.sizes(), "mse: target shape ", t.sizes(),
+              " != output shape ", y.sizes());
   auto yc = y.contiguous();
   auto tc = t.contiguous();
   const int64_t n = yc.numel();
   auto dy = at::empty_like(yc);
   const float* gp = gout_ptr(gout, "mse_bwd");
+  if (n == 0) return dy;
   DISPATCH_F32_BF16(y.scalar_type(), "mse_bwd", {
     hipLaunchKernelGGL((k_mse_bwd<scalar_t>), dim3(cdiv(n, 256)), dim3(256), 0,
                        cur_stream(), cdptr<scalar_t>(yc), cdptr<scalar_t>(tc),
@@ -517,8 +600,25 @@ torch::Tensor build_copy_plan(const std::vector<torch::Tensor>& tensors,
   return plan.to(device);
 }
 
+// The plan rows are raw addresses: all that can be checked here is that the
+// launch reads no more rows than the plan has.
+static void check_copy_plan(const torch::Tensor& bucket,
+                            const torch::Tensor& plan, int64_t total_blocks,
+                            const char* name) {
+  TORCH_CHECK(bucket.is_cuda() && plan.device() == bucket.device(), name,
+              ": bucket and plan must be on one device");
+  TORCH_CHECK(plan.scalar_type() == at::kLong && plan.is_contiguous() &&
+                  plan.dim() == 2 && plan.size(1) == 3,
+              name, ": plan must be a contiguous int64 [blocks,3] tensor");
+  TORCH_CHECK(total_blocks >= 0 && total_blocks <= plan.size(0), name,
+              ": total_blocks ", total_blocks, " outside the plan's ",
+              plan.size(0), " rows");
+}
+
 void flatten_into(torch::Tensor bucket, torch::Tensor plan,
                   int64_t total_blocks, bool zero_src) {
+  check_copy_plan(bucket, plan, total_blocks, "flatten_into");
+  if (total_blocks == 0) return;  // an empty plan copies nothing
   hipLaunchKernelGGL((k_bucket_copy<true>), dim3((uint32_t)total_blocks),
                      dim3(256), 0, cur_stream(),
                      reinterpret_cast<char*>(bucket.data_ptr()),
@@ -527,6 +627,8 @@ void flatten_into(torch::Tensor bucket, torch::Tensor plan,
 }
 
 void unflatten_from(torch::Tensor bucket, torch::Tensor plan, int64_t total_blocks) {
+  check_copy_plan(bucket, plan, total_blocks, "unflatten_from");
+  if (total_blocks == 0) return;
   hipLaunchKernelGGL((k_bucket_copy<false>), dim3((uint32_t)total_blocks),
                      dim3(256), 0, cur_stream(),
                      reinterpret_cast<char*>(bucket.data_ptr()),
@@ -606,9 +708,18 @@ std::vector<torch::Tensor> epoch_shard_multi(torch::Tensor X, torch::Tensor Tg,
                                              int64_t rank, int64_t world) {
   TORCH_CHECK(X.is_cuda() && Tg.is_cuda() && X.is_contiguous() &&
               Tg.is_contiguous());
+  TORCH_CHECK(Tg.device() == X.device() &&
+                  Tg.scalar_type() == X.scalar_type(),
+              "epoch_shard: X and T must share a device and a dtype");
   TORCH_CHECK(epochs >= 1 && epochs <= 1 << 20, "epochs out of range");
+  TORCH_CHECK(X.dim() == 2 && Tg.dim() == 2, "epoch_shard: X must be [n,K] ",
+              "and T [n,1]");
   const int n = (int)X.size(0), K = (int)X.size(1);
   TORCH_CHECK(Tg.size(0) == n && Tg.size(1) == 1, "targets must be [n,1]");
+  TORCH_CHECK(world >= 1 && rank >= 0 && rank < world,
+              "epoch_shard: rank ", rank, " outside world ", world);
+  TORCH_CHECK(world <= n, "epoch_shard: world ", world, " exceeds the ", n,
+              " dataset rows, every shard would be empty");
   const int per_rank = n / (int)world;
   auto xs = at::empty({epochs * per_rank, K}, X.options());
   auto ts = at::empty({epochs * per_rank, 1}, Tg.options());

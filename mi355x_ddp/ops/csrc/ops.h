@@ -17,7 +17,10 @@ torch::Tensor linear_fwd(torch::Tensor x, torch::Tensor w,
 
 // dw = dy^T @ x, db = sum_i dy  (reference: loss.backward(), single_gpu.py:25)
 // dw/db may be preallocated views into a gradient bucket; accumulate=true
-// adds into them instead of overwriting.
+// adds into them instead of overwriting. An empty db skips the bias gradient.
+// Like every launcher here it checks dtype, shape and device of all operands
+// before the launch, and empty work (no rows, no elements, an empty plan)
+// returns torch's empty result without one.
 void linear_bwd_weight(torch::Tensor x, torch::Tensor dy,
                        torch::Tensor dw, torch::Tensor db, bool accumulate);
 
