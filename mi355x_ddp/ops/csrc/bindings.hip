@@ -44,7 +44,7 @@ class ToyShardRun : public std::enable_shared_from_this<ToyShardRun> {
     TORCH_CHECK(dt == at::kFloat || dt == at::kBFloat16,
                 "ToyShardRun: flat_param must be f32 or bf16, got ", dt);
     bf16_ = dt == at::kBFloat16;
-    TORCH_CHECK(lr > 0.0, "ToyShardRun applies SGD in-kernel: lr must be > 0");
+    TORCH_CHECK(lr_ > 0.f, "ToyShardRun applies SGD in-kernel: lr must be > 0");
     TORCH_CHECK(w_off >= 0 && b_off >= 0 && b_off < param_.numel() &&
                     w_off < param_.numel(),
                 "ToyShardRun: w_off/b_off outside flat_param");
@@ -70,31 +70,16 @@ class ToyShardRun : public std::enable_shared_from_this<ToyShardRun> {
 
   void bind_shard(torch::Tensor xs, torch::Tensor ts, int64_t batch) {
     TORCH_CHECK(!recorder_, "a recorder binds step counts: use bind_steps");
-    TORCH_CHECK(xs.is_cuda() && ts.is_cuda() &&
-                    xs.device() == param_.device() &&
-                    ts.device() == param_.device(),
-                "bind_shard: xs/ts must be on flat_param's device");
-    TORCH_CHECK(xs.dim() == 2 && xs.is_contiguous() && ts.is_contiguous(),
-                "bind_shard: xs must be [rows, K], xs/ts contiguous");
-    TORCH_CHECK(xs.scalar_type() == param_.scalar_type() &&
-                    ts.scalar_type() == param_.scalar_type(),
-                "bind_shard: xs/ts dtype must match flat_param");
-    TORCH_CHECK(ts.dim() >= 1 && ts.size(0) == xs.size(0) &&
-                    ts.numel() == ts.size(0),
-                "bind_shard: ts must hold one target per row of xs");
-    const int64_t K = xs.size(1);
-    TORCH_CHECK(batch >= 1 && batch <= 128 && K >= 1 && K <= 32,
-                "toy multistep supports B<=128, K<=32");
-    TORCH_CHECK(xs.size(0) % batch == 0,
-                "bind_shard: rows must be a multiple of batch");
-    TORCH_CHECK(w_off_ + K <= param_.numel(),
-                "bind_shard: K weights do not fit flat_param at w_off");
+    TORCH_CHECK(batch >= 1, "bind_shard: batch must be >= 1");
+    // the entry points' own validator (toy_kernels.hip), once per bind
+    const ToyDims d = toy_check_args("bind_shard", xs, ts, param_, nullptr,
+                                     false, loss_, w_off_, b_off_, batch);
     run_.launch_pending();  // what is pending runs on the OLD shard
     xs_ = std::move(xs);
     ts_ = std::move(ts);
-    B_ = (int)batch;
-    K_ = (int)K;
-    run_.bind(xs_.size(0) / batch);
+    B_ = d.B;
+    K_ = d.K;
+    run_.bind(d.S);
   }
 
   void bind_steps(int64_t steps_bound) {

@@ -118,6 +118,10 @@ void unflatten_from(torch::Tensor bucket, torch::Tensor plan, int64_t total_bloc
 // toy path, SURVEY §7 hard-part 2).
 // lr > 0: apply the SGD update in-kernel (world-size-1 single-launch step);
 // lr <= 0: write gradients into grad_flat for the all-reduce path.
+// With lr > 0 grad_flat is never touched and may be left out, which means an
+// undefined or an EMPTY tensor (torch.Tensor() from Python). Any non-empty
+// grad_flat is checked like param_flat (toy_check_args below) whatever lr
+// is: a placeholder of another dtype, device or size is refused.
 void toy_fused_fwd_bwd(torch::Tensor x, torch::Tensor t,
                        torch::Tensor param_flat, torch::Tensor grad_flat,
                        torch::Tensor loss_out, bool use_mse,
@@ -162,6 +166,24 @@ void toy_multistep_launch(const void* x, const void* t, void* param,
                           float lr, int B, int K, int S, bool bf16);
 // Validated pointer of the optional f32 loss output (nullptr when empty).
 float* toy_loss_ptr(const torch::Tensor& loss_out);
+
+// The argument check shared by every toy entry point, complete before any
+// launch: x [rows, K] contiguous f32/bf16 on a GPU; t contiguous with one
+// target per row; param (and grad, where given) contiguous, of x's dtype, on
+// x's device; 1 <= batch <= 128 dividing rows (batch < 0: the whole of x),
+// 1 <= K <= 32; w_off, b_off >= 0 with [w_off, w_off + K) and b_off inside
+// the bucket and b_off outside the weights; loss_out empty or f32 on x's
+// device. grad == nullptr: no gradient bucket; need_grad: it must be given,
+// i.e. defined and not empty (the single step with lr <= 0 writes it).
+// S == 0: nothing to run.
+struct ToyDims {
+  int B, K, S;
+};
+ToyDims toy_check_args(const char* who, const torch::Tensor& x,
+                       const torch::Tensor& t, const torch::Tensor& param,
+                       const torch::Tensor* grad, bool need_grad,
+                       const torch::Tensor& loss_out, int64_t w_off,
+                       int64_t b_off, int64_t batch);
 
 // Process-wide kernel selector for the fp32 batch-32/64, K-20 multi-step
 // fast path: "chain" (lane-parallel fmaf chains on the vector ALU, the

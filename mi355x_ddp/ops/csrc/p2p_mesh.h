@@ -51,6 +51,9 @@ class P2pMesh {
 
   int rank() const { return rank_; }
   int world() const { return world_; }
+  // connect() has filled the peer slot table: before that it holds no
+  // addresses, and no kernel may be given it
+  bool connected() const { return connected_; }
 
   // device-view accessors for kernels that embed the mesh exchange
   // (toy_multistep_mesh in toy_kernels.hip)
@@ -73,6 +76,7 @@ class P2pMesh {
   unsigned int* err_host_ = nullptr;   // pinned host flag
   unsigned long long seq_ = 0;
   bool fine_grained_ = false;
+  bool connected_ = false;
 };
 
 }  // namespace mi355x

@@ -116,11 +116,13 @@ void P2pMesh::connect(const std::vector<std::string>& handles) {
   }
   HIP_OK(hipMemcpy(peer_slot_dev_, slots.data(),
                    sizeof(MeshSlot*) * world_, hipMemcpyHostToDevice));
+  connected_ = true;
 }
 
 void P2pMesh::all_reduce_avg_inline(torch::Tensor t) {
   TORCH_CHECK(t.is_cuda() && t.is_contiguous(), "mesh: contiguous cuda only");
   TORCH_CHECK(t.numel() <= 64, "mesh all-reduce is the tiny-payload path");
+  TORCH_CHECK(connected_, "mesh: connect() has not run");
   const int n = (int)t.numel();
   ++seq_;
   const float inv = 1.f / (float)world_;

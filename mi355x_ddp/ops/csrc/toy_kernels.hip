@@ -1418,15 +1418,68 @@ static float* loss_ptr(const torch::Tensor& loss_out) {
   return loss_out.data_ptr<float>();
 }
 
-// Checks shared by toy_multistep and toy_multistep_mesh; returns the step
-// count S (0: nothing to launch).
-static int multistep_steps(const torch::Tensor& x, const torch::Tensor& t,
-                           int B, double lr, const char* lr_msg) {
-  TORCH_CHECK(x.is_contiguous() && t.is_contiguous());
-  TORCH_CHECK(x.size(0) % B == 0, "x rows must be a multiple of batch");
-  TORCH_CHECK(t.size(0) == x.size(0), "t rows must match x rows");
-  TORCH_CHECK(lr > 0.0, lr_msg);
-  return (int)(x.size(0) / B);
+// The one argument check of every toy entry point (toy_fused_fwd_bwd,
+// toy_multistep, toy_multistep_mesh, ToyShardRun::bind_shard), run to the
+// end BEFORE anything is launched or any other state is touched: the
+// kernels take raw pointers and offsets on trust, so whatever passes here
+// must keep every device access inside the tensors given.
+//   batch < 0   the whole of x is one batch (the single step)
+//   grad        nullptr: the entry point has no gradient bucket. Otherwise
+//               checked like param when given (defined and not empty),
+//               and required (need_grad) where the kernel writes it: the
+//               single step with lr <= 0.
+//   loss_out    undefined or empty: no loss wanted; else f32, >= 1 element
+// Returns (B, K, S); S == 0 (no rows) means nothing to launch.
+ToyDims toy_check_args(const char* who, const torch::Tensor& x,
+                       const torch::Tensor& t, const torch::Tensor& param,
+                       const torch::Tensor* grad, bool need_grad,
+                       const torch::Tensor& loss_out, int64_t w_off,
+                       int64_t b_off, int64_t batch) {
+  TORCH_CHECK(x.defined() && t.defined() && param.defined(), who,
+              ": x, t and param_flat must be tensors");
+  TORCH_CHECK(x.is_cuda(), who, ": x must be on a GPU");
+  const auto dev = x.device();
+  const auto dt = x.scalar_type();
+  TORCH_CHECK(dt == at::kFloat || dt == at::kBFloat16, who,
+              ": dtype must be f32 or bf16, got ", dt);
+  TORCH_CHECK(x.dim() == 2 && x.is_contiguous(), who,
+              ": x must be [rows, K] and contiguous");
+  const int64_t rows = x.size(0), K = x.size(1);
+  TORCH_CHECK(t.device() == dev && t.scalar_type() == dt && t.is_contiguous() &&
+                  t.numel() == rows,
+              who, ": t must be contiguous, one target per row of x, with "
+              "x's dtype and device");
+  TORCH_CHECK(K >= 1 && K <= 32, who, " supports 1 <= K <= 32, got K = ", K);
+  if (batch < 0) batch = rows > 0 ? rows : 1;
+  TORCH_CHECK(batch >= 1 && batch <= 128, who,
+              " supports 1 <= batch <= 128, got batch = ", batch);
+  TORCH_CHECK(rows % batch == 0 && rows / batch <= INT32_MAX, who,
+              ": x rows must be a multiple of batch");
+  auto check_bucket = [&](const torch::Tensor& b, const char* name) {
+    TORCH_CHECK(b.device() == dev && b.scalar_type() == dt &&
+                    b.is_contiguous(),
+                who, ": ", name, " must be contiguous with x's dtype and device");
+    const int64_t n = b.numel();
+    TORCH_CHECK(n <= INT32_MAX && w_off >= 0 && b_off >= 0 &&
+                    w_off + K <= n && b_off < n,
+                who, ": w_off/b_off with K = ", K, " fall outside ", name,
+                " (", n, " elements)");
+    TORCH_CHECK(b_off < w_off || b_off >= w_off + K, who,
+                ": b_off lies inside the weights [w_off, w_off + K)");
+  };
+  check_bucket(param, "param_flat");
+  if (grad != nullptr) {
+    // "not given" is an undefined or an empty tensor, as for loss_out
+    const bool given = grad->defined() && grad->numel() > 0;
+    TORCH_CHECK(given || !need_grad, who,
+                ": lr <= 0 writes the gradients: grad_flat is required");
+    if (given) check_bucket(*grad, "grad_flat");
+  }
+  if (loss_out.defined() && loss_out.numel() > 0)
+    TORCH_CHECK(loss_out.device() == dev &&
+                    loss_out.scalar_type() == at::kFloat,
+                who, ": loss_out must be f32 on x's device");
+  return {(int)batch, (int)K, (int)(rows / batch)};
 }
 
 template <typename T>
@@ -1477,30 +1530,36 @@ float* toy_loss_ptr(const torch::Tensor& loss_out) { return loss_ptr(loss_out); 
 void toy_multistep(torch::Tensor x, torch::Tensor t, torch::Tensor param_flat,
                    torch::Tensor loss_out, bool use_mse,
                    int64_t w_off, int64_t b_off, double lr, int64_t batch) {
-  const int B = (int)batch, K = (int)x.size(1);
-  TORCH_CHECK(B <= 128 && K <= 32, "toy multistep supports B<=128, K<=32");
-  const int S = multistep_steps(
-      x, t, B, lr, "toy_multistep is the world-1 in-kernel-SGD path");
-  if (S == 0) return;
-  float* lossp = loss_ptr(loss_out);
-  const auto dt = x.scalar_type();
-  TORCH_CHECK(dt == at::kFloat || dt == at::kBFloat16,
-              "toy_multistep: unsupported dtype ", dt);
+  TORCH_CHECK(batch >= 1, "toy_multistep: batch must be >= 1");
+  const ToyDims d = toy_check_args("toy_multistep", x, t, param_flat, nullptr,
+                                   false, loss_out, w_off, b_off, batch);
+  TORCH_CHECK((float)lr > 0.f,
+              "toy_multistep is the world-1 in-kernel-SGD path: lr must be > 0");
+  if (d.S == 0) return;
   toy_multistep_launch(x.data_ptr(), t.data_ptr(), param_flat.data_ptr(),
-                       lossp, use_mse, (int)w_off, (int)b_off, (float)lr, B,
-                       K, S, dt == at::kBFloat16);
+                       loss_ptr(loss_out), use_mse, (int)w_off, (int)b_off,
+                       (float)lr, d.B, d.K, d.S,
+                       x.scalar_type() == at::kBFloat16);
 }
 
 void toy_multistep_mesh(torch::Tensor x, torch::Tensor t,
                         torch::Tensor param_flat, torch::Tensor loss_out,
                         bool use_mse, int64_t w_off, int64_t b_off, double lr,
                         int64_t batch, P2pMesh& mesh) {
-  const int B = (int)batch, K = (int)x.size(1);
-  TORCH_CHECK((B == 32 || B == 64) && K == 20,
+  // everything is checked before the mesh is touched: a sequence range
+  // taken for a launch that never happens would desynchronise the ranks
+  TORCH_CHECK(batch >= 1, "toy_multistep_mesh: batch must be >= 1");
+  const ToyDims d = toy_check_args("toy_multistep_mesh", x, t, param_flat,
+                                   nullptr, false, loss_out, w_off, b_off,
+                                   batch);
+  const int B = d.B, S = d.S;
+  TORCH_CHECK((B == 32 || B == 64) && d.K == 20,
               "mesh multistep supports the fast-path shapes "
               "(batch 32 or 64, K 20)");
-  const int S = multistep_steps(x, t, B, lr,
-                                "mesh multistep applies SGD in-kernel");
+  TORCH_CHECK((float)lr > 0.f,
+              "mesh multistep applies SGD in-kernel: lr must be > 0");
+  TORCH_CHECK(mesh.connected(),
+              "toy_multistep_mesh: the mesh is not connected");
   if (S == 0) return;
   float* lossp = loss_ptr(loss_out);
   const MeshArgs m{mesh.peer_slots(), mesh.my_mb(), mesh.world(),
@@ -1515,8 +1574,7 @@ void toy_multistep_mesh(torch::Tensor x, torch::Tensor t,
     });
   };
   if (x.scalar_type() == at::kFloat) go(float{});
-  else if (x.scalar_type() == at::kBFloat16) go(__hip_bfloat16{});
-  else TORCH_CHECK(false, "mesh multistep: dtype must be f32 or bf16");
+  else go(__hip_bfloat16{});
   HIP_OK(hipGetLastError());
 }
 
@@ -1528,7 +1586,9 @@ static void launch_toy_fused(const torch::Tensor& x, const torch::Tensor& t,
   const T* xp = cdptr<T>(x);
   const T* tp = cdptr<T>(t);
   T* pp = dptr<T>(param_flat);
-  T* gp = dptr<T>(grad_flat);
+  // not given (lr > 0 only, checked): the kernel never touches it
+  T* gp = grad_flat.defined() && grad_flat.numel() ? dptr<T>(grad_flat)
+                                                   : nullptr;
   with_toy_tiles(B, K, [&](auto mt, auto kt) {
     hipLaunchKernelGGL((k_toy_fused<T, decltype(mt)::value, decltype(kt)::value>),
                        dim3(1), dim3(64), 0, cur_stream(), xp, tp, pp, gp,
@@ -1540,9 +1600,13 @@ void toy_fused_fwd_bwd(torch::Tensor x, torch::Tensor t,
                        torch::Tensor param_flat, torch::Tensor grad_flat,
                        torch::Tensor loss_out, bool use_mse,
                        int64_t w_off, int64_t b_off, double lr) {
-  const int B = (int)x.size(0), K = (int)x.size(1);
-  TORCH_CHECK(B <= 128 && K <= 32, "toy fused kernel supports B<=128, K<=32");
-  TORCH_CHECK(x.is_contiguous() && t.is_contiguous());
+  // the kernel chooses its branch on the f32 lr: one that rounds to zero
+  // writes gradients like any lr <= 0
+  const ToyDims d = toy_check_args("toy_fused_fwd_bwd", x, t, param_flat,
+                                   &grad_flat, !((float)lr > 0.f), loss_out,
+                                   w_off, b_off, -1);
+  if (d.S == 0) return;
+  const int B = d.B, K = d.K;
   float* lossp = loss_ptr(loss_out);
   DISPATCH_F32_BF16(x.scalar_type(), "toy_fused_fwd_bwd", {
     launch_toy_fused<scalar_t>(x, t, param_flat, grad_flat, lossp, use_mse,

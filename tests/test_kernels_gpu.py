@@ -193,7 +193,8 @@ def test_toy_fused_step_matches_reference(B, K):
 
 @pytest.mark.parametrize("B,K", TOY_SHAPES)
 def test_toy_fused_inkernel_sgd(B, K):
-    # lr > 0 path: one launch does fwd+bwd+SGD; matches torch step exactly
+    # lr > 0 path: one launch does fwd+bwd+SGD; agrees with torch's fp32 step
+    # to atol 1e-5 (the derived fp64 bound: test_toy_step_oracle_gpu.py)
     LR = 0.1
     x = _rand(B, K, seed=40).to(DEV)
     t = _rand(B, 1, seed=41).to(DEV)
