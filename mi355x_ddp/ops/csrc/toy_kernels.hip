@@ -996,11 +996,36 @@ struct ChainSlot {
 // latency (~900 cycles) hides behind kChainTilesAhead tiles of loader work.
 static constexpr int kChainTilesAhead = 4;
 
-// One workgroup: wave 0 computes, waves 1..NL load. The loaders stage each
-// [B][K] tile (coalesced dword loads on the flat index, so no alignment
-// requirement on the base) into an LDS ring of two halves of H slots; the
-// compute wave works through half c & 1 (chunk c = steps cH .. cH + H - 1)
-// while the loaders fill the other half with chunk c + 1.
+// One workgroup of four waves, one per SIMD. Wave 0 computes; the waves
+// whose bit is set in LMASK load; any other wave is parked (it executes the
+// barriers and nothing else). The loaders stage each [B][K] tile (dword
+// loads, so no alignment requirement on the base) into an LDS ring of two
+// halves of H slots; the compute wave works through half c & 1 (chunk c =
+// steps cH .. cH + H - 1) while the loaders fill the other half with chunk
+// c + 1.
+//
+// Roles follow the wave index because SIMD placement does: a workgroup's
+// waves go to SIMDs in the cyclic order 0 -> 2 -> 1 -> 3 from a start that
+// varies per launch, so waves 0 and 2 always share one half of the CU's LDS
+// store path (SIMDs {0,1} or {2,3}) and waves 1 and 3 the other (read back
+// from HW_ID over 24 launches, profiles r09a). A loader on the compute
+// wave's half puts its store traffic in the way of the compute wave's read
+// addresses, so the loaders are waves 1 and 3 and wave 2 is the parked one.
+//
+// Loader lane-to-element map. A 32-lane group of a ds_write_b32 is served
+// in one pass when it touches each of the 32 banks at most twice. In the
+// transposed image (pitch = 4 mod 32 dwords) element (row, k) lies in bank
+// (4 k + row) mod 32, so a group covers a block of 4 rows x 8 k (lane l:
+// row l / 8, k l % 8: 32 distinct banks) for k < 16, and a block of 8 rows
+// x 4 k (row l / 4, k 16 + l % 4: banks c .. c + 19, twelve of them twice)
+// for k = 16..19. In the row image (bank (20 row + k) mod 32) the 4 x 8
+// blocks hit four banks twice and the 8 x 4 blocks every bank once. The
+// 2-way passes still count as LDS-array cycles (SQ_LDS_BANK_CONFLICT: 20
+// per tile at batch 32, 36 with the flat-index walk, profiles r09a). The G = 2 NL groups of the loaders take G such blocks
+// per element index i, stacked along the rows, so a lane's elements differ
+// by compile-time constants in global memory and in both images. The price
+// is global loads in 32-byte (16-byte) runs in place of 256-byte ones, on a
+// tile of 2.5 KB that the loaders fetch four steps ahead.
 //
 // Barrier protocol. Barrier c (c = 0 .. NC - 1, NC = ceil(S / H)) is the
 // only synchronisation, and every wave executes exactly NC of them, a
@@ -1017,27 +1042,59 @@ static constexpr int kChainTilesAhead = 4;
 // of the last chunk skips keep stale data that the compute wave, which
 // reads steps < S only, never consumes. The run-ahead loads past the end
 // re-read tile S - 1 into registers that are never written out.
-template <int B_, int K_, int NL>
-__global__ void __launch_bounds__(64 * (1 + NL))
+static constexpr int kChainWaves = 4;
+template <int B_, int K_, unsigned LMASK>
+__global__ void __launch_bounds__(64 * kChainWaves)
 k_toy_multistep_chain(const float* __restrict__ X,
                       const float* __restrict__ Tg,
                       float* __restrict__ param, float* __restrict__ loss_out,
                       int S, int H, int use_mse, int w_off, int b_off,
                       float lr) {
-  static_assert((B_ == 32 || B_ == 64) && K_ == 20 && NL >= 1 && NL <= 3,
-                "chain path: B in {32, 64}, K = 20, one wave per SIMD");
+  constexpr int NL = __builtin_popcount(LMASK);  // loader waves
+  constexpr int G = 2 * NL;                      // their 32-lane groups
+  static_assert((B_ == 32 || B_ == 64) && K_ == 20 && (LMASK & 1u) == 0 &&
+                    LMASK < (1u << kChainWaves) && (NL == 1 || NL == 2),
+                "chain path: B in {32, 64}, K = 20, wave 0 computes, one or "
+                "two of waves 1..3 load");
+  static_assert((B_ / 4) % G == 0 && (B_ / 8) % G == 0,
+                "the loader groups tile the rows exactly");
   using L = ChainSlot<B_, K_>;
   __shared__ __attribute__((aligned(16))) float ring[2 * L::kMaxH * L::kSize];
   // scalar wave index: the role branch is uniform, EXEC stays full
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 
+  if (wave != 0 && !((LMASK >> wave) & 1u)) {
+    // ---------------- parked wave ----------------
+    const int NC = (S + H - 1) / H;
+    for (int c = 0; c < NC; ++c) __syncthreads();
+    return;
+  }
   if (wave != 0) {
     // ---------------- loader waves ----------------
-    constexpr int NT = 64 * NL;                     // loader threads
-    constexpr int NX = (B_ * K_ + NT - 1) / NT;     // X dwords per lane/tile
-    constexpr bool kTail = (B_ * K_) % NT != 0;     // last dword partial
+    // X dwords per lane and tile: NXA from the 4-row x 8-k blocks (k < 16),
+    // NXB from the 8-row x 4-k blocks (k = 16..19)
+    constexpr int RPI = B_ / 4 / G;  // 4-row blocks a lane has per 8 k
+    constexpr int NXA = 2 * RPI, NXB = B_ / 8 / G, NX = NXA + NXB;
+    static_assert(NX * 64 * NL == B_ * K_, "every element exactly once");
     constexpr int R = kChainTilesAhead;
-    const int lt = (int)threadIdx.x - 64;
+    // thread index among the loaders: 64 x (rank of the wave in LMASK) + lane
+    const int lt = 64 * __builtin_popcount(LMASK & ((1u << wave) - 1u)) +
+                   (int)(threadIdx.x & 63);
+    const int g = lt >> 5, l = lt & 31;
+    const int rowA = 4 * g + (l >> 3), kA = l & 7;
+    const int rowB = 8 * g + (l >> 2), kB = 16 + (l & 3);
+    // element i of this lane as a dword offset in the [B][K] tile (the row
+    // image is the tile itself) and in the transposed image; rows < B_ and
+    // k < K_ by construction
+    auto row_off = [&](int i) {
+      return i < NXA ? (rowA + 4 * G * (i % RPI)) * K_ + kA + 8 * (i / RPI)
+                     : (rowB + 8 * G * (i - NXA)) * K_ + kB;
+    };
+    auto tr_off = [&](int i) {
+      return i < NXA
+                 ? (kA + 8 * (i / RPI)) * L::kPitch + rowA + 4 * G * (i % RPI)
+                 : kB * L::kPitch + rowB + 8 * G * (i - NXA);
+    };
     const int total = (S + H - 1) / H * H;  // NC whole chunks
     float xv[R][NX], tv[R];
 
@@ -1049,27 +1106,34 @@ k_toy_multistep_chain(const float* __restrict__ X,
       const int tc = tile < S ? tile : S - 1;
       const float* xt = X + (size_t)tc * (B_ * K_);
 #pragma unroll
-      for (int i = 0; i < NX; ++i) {
-        const int f = lt + i * NT;
-        x[i] = xt[(kTail && i == NX - 1 && f >= B_ * K_) ? B_ * K_ - 1 : f];
-      }
+      for (int i = 0; i < NX; ++i) x[i] = xt[row_off(i)];
       t = Tg[(size_t)tc * B_ + (lt & (B_ - 1))];
     };
     auto write_tile = [&](const float (&x)[NX], float t, int slot) {
       float* sl = ring + slot * L::kSize;
 #pragma unroll
       for (int i = 0; i < NX; ++i) {
-        const int f = lt + i * NT;
-        if (!kTail || i < NX - 1 || f < B_ * K_) {
-          sl[L::kRow + f] = x[i];
-          sl[L::kTr + (f % K_) * L::kPitch + f / K_] = x[i];
-        }
+        sl[L::kRow + row_off(i)] = x[i];
+        sl[L::kTr + tr_off(i)] = x[i];
       }
       if (lt < B_) sl[L::kTgt + lt] = t;
     };
 
+    // The first R tiles, issued tile by tile as the loop below issues them:
+    // vmcnt counts in issue order, and left to itself the scheduler groups
+    // these loads by address register across the tiles, after which the
+    // loop's waits for "the oldest tile" drain most of the run-ahead
+    // (vmcnt(16), (7), (3) where (23) .. (18) are meant; 186 ns/step
+    // against 171 at batch 32). Nothing but the listing shows a relapse:
+    // after a compiler change, look at the s_waitcnt vmcnt in front of the
+    // ds_write_b32 of the loaders' tile loop (device-only -S -O3). Each of
+    // the R unrolled tiles must wait with vmcnt(R (NX + 1) - 1) falling to
+    // vmcnt((R - 1)(NX + 1)): 23 .. 18 at batch 32, 43 .. 33 at batch 64.
 #pragma unroll
-    for (int r = 0; r < R; ++r) load_tile(xv[r], tv[r], r);
+    for (int r = 0; r < R; ++r) {
+      load_tile(xv[r], tv[r], r);
+      __builtin_amdgcn_sched_barrier(0);
+    }
     if (lt < B_)
       for (int sl = 0; sl < 2 * H; ++sl) ring[sl * L::kSize + L::kOnes + lt] = 1.f;
     int slot = 0, togo = H;
@@ -1339,16 +1403,26 @@ void set_toy_multistep_chain_depth(int64_t depth) {
 
 // The chain depth is H, the steps per ring half (one barrier per H steps),
 // a runtime kernel argument clamped to what 64 KB of LDS holds (5 at batch
-// 32, 2 at batch 64). Measured at batch 32 (profiles r07a), H = 2 / 3 / 4:
-// S = 1024 -> 177 / 174 / 175 ns/step, S = 64 -> 210 / 210 / 215 (a launch
-// cannot start before its first H tiles are staged), so the default stays
-// the smallest ring, which is all batch 64 can hold. With the compute
-// wave's step at 84 instructions one loader wave no longer keeps up at
-// batch 32 (231 ns/step against 177 with two); a third gains nothing at
-// either batch size.
-static constexpr int kChainDefaultH = 2;
-static constexpr int kChainLoaderWaves32 = 2;
-static constexpr int kChainLoaderWaves64 = 2;
+// 32, 2 at batch 64). Measured at batch 32 with the loaders below (profiles
+// r09a), H = 2 / 3 / 4: S = 1024 -> 172 / 167 / 166 ns/step, S = 64 -> 206 /
+// 204 / 208 (a launch cannot start before its first H tiles are staged),
+// S <= 32 equal within the spread of a launch. Up to r07a the depth bought
+// 1 to 3 ns and the default was 2; with the loaders' stores out of the
+// compute wave's way what is left at H = 2 is a loader arriving late at a
+// barrier now and then, which a third slot per half absorbs. Batch 64 holds
+// two.
+static constexpr int kChainDefaultH = 3;
+// The loader set, as a mask of wave indices: waves 1 and 3, the two that
+// never share the compute wave's half of the LDS store path (the kernel's
+// comment). Measured (r09a), S = 1024 / 64, ns/step at H = 2:
+//   batch 32   waves {1,3} 172 / 206   {1,2} 174 / 207   {1} 189 / 224
+//   batch 64   waves {1,3} 286 / 322   {1,2} 292 / 328   {1} 283 / 325
+// One loader wave keeps up at batch 64 (a step is 670 cycles there) and not
+// at batch 32; two are kept at both, for batch 64's short launches. A third
+// loader would have to be wave 2: with the old store map that gave 180 / 215
+// and 297 / 336.
+static constexpr unsigned kChainLoaders32 = 0b1010;
+static constexpr unsigned kChainLoaders64 = 0b1010;
 
 template <int B_>
 static void launch_toy_multistep_chain(const float* xp, const float* tp,
@@ -1359,10 +1433,10 @@ static void launch_toy_multistep_chain(const float* xp, const float* tp,
   int H = g_chain_depth.load();
   if (H == 0) H = kChainDefaultH;
   if (H > kMaxH) H = kMaxH;
-  constexpr int NL = B_ == 64 ? kChainLoaderWaves64 : kChainLoaderWaves32;
-  hipLaunchKernelGGL((k_toy_multistep_chain<B_, 20, NL>), dim3(1),
-                     dim3(64 * (1 + NL)), 0, cur_stream(), xp, tp, pp, lossp,
-                     S, H, use_mse ? 1 : 0, w_off, b_off, lr);
+  constexpr unsigned LM = B_ == 64 ? kChainLoaders64 : kChainLoaders32;
+  hipLaunchKernelGGL((k_toy_multistep_chain<B_, 20, LM>), dim3(1),
+                     dim3(64 * kChainWaves), 0, cur_stream(), xp, tp, pp,
+                     lossp, S, H, use_mse ? 1 : 0, w_off, b_off, lr);
 }
 
 // fn(integral_constant<int, B>) for the two fast-path batch sizes
