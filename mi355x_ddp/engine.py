@@ -11,7 +11,9 @@ bound (SURVEY §7 hard-part 2). Three engines, in increasing aggression:
 - `PersistentToyStep` (the bench default): DEFERRED runs of consecutive
   steps execute as one multi-step kernel with the weights LDS-resident;
   at world > 1 with a `P2pMeshComm` the kernel performs an in-kernel xGMI
-  mesh all-reduce per step. See docs/KERNELS.md.
+  mesh all-reduce per step. The runs are tracked, ordered and launched by
+  the extension's `ToyShardRun`; the class is a thin wrapper. See
+  docs/KERNELS.md.
 
 All engines train the SAME model parameters the generic autograd path
 trains: the Reducer's flat bucket is shared state, so checkpoints and the
@@ -121,6 +123,28 @@ def _recover_failed_capture(ctx):
     torch.cuda.synchronize()
 
 
+def _capture_graph(body, on_failure: str):
+    """body() captured in a new hipGraph. None when an earlier capture in
+    this process failed (capturing again is lethal, see _CAPTURE_POISONED)
+    or when this one does: it then warns with on_failure (formatted with
+    the exception as `e`), poisons further captures and cleans up. The
+    caller runs eager from there on."""
+    if _CAPTURE_POISONED:
+        return None
+    g = torch.cuda.CUDAGraph()
+    ctx = torch.cuda.graph(g)
+    try:
+        with ctx:
+            body()
+        return g
+    except Exception as e:
+        import warnings
+        warnings.warn(on_failure.format(e=e), RuntimeWarning, stacklevel=3)
+        _poison_captures(g)
+        _recover_failed_capture(ctx)
+        return None
+
+
 class ToyFusedStep:
     """One-kernel fwd+bwd for HipLinear(K,1) + MSE/CE, bucket all-reduce,
     fused SGD. Works for any world size (comm=None -> single process)."""
@@ -164,28 +188,35 @@ class ToyFusedStep:
 
 class PersistentToyStep(ToyFusedStep):
     """Deferred-launch engine: runs of consecutive steps execute as ONE
-    multi-step kernel launch (`toy_multistep`), weights resident in LDS
-    across steps. Works at world 1 (no communicator) and, with a
-    `P2pMeshComm`, at any world size — the kernel then performs one
-    in-kernel xGMI mesh all-reduce per step (`toy_multistep_mesh`).
+    multi-step kernel launch, weights resident in LDS across steps. Works
+    at world 1 (no communicator) and, with a `P2pMeshComm`, at any world
+    size: the kernel then performs one in-kernel xGMI mesh all-reduce per
+    step.
 
-    `step(x, t)` defers when the incoming batch is the next contiguous
-    [B, K] slice of the same device buffer (the device-resident epoch
-    shard, bench.py DeviceData); any other batch flushes the pending run
-    and starts a new one. Per-step arithmetic is bitwise-identical to the
-    single-step fused kernel, so deferral changes WHEN work is launched,
-    never what is computed. Callers must call `flush()` before
-    synchronizing the stream for timing/reading params — bench.py does
-    before every barrier. Deferred-run length is capped by `max_defer`.
+    A thin wrapper over the extension's `ToyShardRun`, which tracks both
+    kinds of deferred run, keeps them in submission order and launches from
+    raw pointers (docs/KERNELS.md, "The shard-bound stepper"):
 
-    At world 1 the shard-bound protocol (`bind_shard` / `step_shard(i)` /
-    `flush`) is the extension's `ToyShardRun`: `step_shard` is a C function
-    and a launch is made from raw pointers. After a `flush()` — the caller
-    is about to synchronize, so the GPU will be idle — the first launches
-    are short and grow (`ramp_first` steps, then times `ramp_growth` per
-    launch up to `max_defer`; `ramp_first=0` for none), so the GPU starts
-    at once instead of waiting for the host to count `max_defer` steps.
-    An index outside the bound shard raises IndexError.
+    - `step(x, t)` defers when the batch is the next contiguous [B, K] slice
+      of the same device buffer as the pending run; any other batch launches
+      what is pending and starts a new run. A batch that is not contiguous
+      on the device runs eagerly, after what was submitted before it.
+    - `bind_shard` / `step_shard(i)` step through a bound epoch shard by
+      batch index (the path bench.py drives); `step_shard` is a C function.
+      An index outside the bound shard raises IndexError before anything is
+      launched for it.
+    - `flush()` launches what is pending. Callers must flush before
+      synchronizing the stream for timing or reading params: bench.py does
+      before every barrier.
+
+    Per-step arithmetic is bitwise-identical to the single-step fused
+    kernel, so deferral changes WHEN work is launched, never what is
+    computed. A run is launched when it reaches `max_defer` steps. At world
+    1 the index run's first launches after a `flush()` (the caller is about
+    to synchronize, so the GPU will be idle) are short and grow: `ramp_first`
+    steps, then times `ramp_growth` per launch up to `max_defer`. With a
+    mesh there is no ramp: every rank must issue the same launches in the
+    same order, so the schedule depends on the submitted steps alone.
 
     With track_loss=True, loss_out holds the LAST executed step's loss.
     """
@@ -200,167 +231,34 @@ class PersistentToyStep(ToyFusedStep):
         assert self.comm is None or self._mesh is not None, \
             "PersistentToyStep needs world 1 or a P2pMeshComm"
         self.max_defer = max_defer
-        self.ramp_first = ramp_first
+        self.ramp_first = ramp_first if self._mesh is None else 0
         self.ramp_growth = ramp_growth
-        self._install_fast_path()
+        self._run = run = ops.ext().ToyShardRun(
+            self.flat_param, self.loss_out, self.use_mse, self.w_off,
+            self.b_off, self.lr, max_defer, self.ramp_first, ramp_growth,
+            self._mesh)
+        self.bind_shard = run.bind_shard
+        self.step_shard = run.step_shard  # the C function itself
+        self.flush = run.flush
 
     @property
     def launch_count(self) -> int:
-        """Kernel launches issued (bench transparency): the generic and
-        mesh paths' own plus the native stepper's."""
+        """Kernel launches issued by the run tracker (bench transparency)."""
+        return self._run.launch_count
+
+    def step(self, x: torch.Tensor, t: torch.Tensor) -> None:
         run = self._run
-        return self._launches + (run.launch_count if run is not None else 0)
-
-    def _install_fast_path(self) -> None:
-        """step/flush as closures over cell variables: the per-step cost is
-        two data_ptr() calls and a shape compare, no attribute traffic.
-        The fp32 kernel takes under 200 ns per step, which is what a Python
-        closure call costs, so at world 1 the shard-bound protocol
-        (bind_shard/step_shard/flush, the path bench.py drives) does not
-        run here at all: it is the extension's ToyShardRun, whose
-        step_shard is a bare C function and whose launches ramp up after a
-        flush (docs/KERNELS.md, "The shard-bound stepper"). The mesh path
-        keeps the Python tracker below: every rank must issue the same
-        collectives in the same order, so its launch pattern stays fixed."""
-        ext_mod = ops.ext() if ops.has_ext() else None
-        flat_param = self.flat_param
-        loss_out = self.loss_out
-        use_mse, w_off, b_off = self.use_mse, self.w_off, self.b_off
-        lr, max_defer = self.lr, self.max_defer
-        mesh = self._mesh
-
-        self._launches = 0
-        self._run = run = None
-        if mesh is None and ext_mod is not None and flat_param.is_cuda:
-            self._run = run = ext_mod.ToyShardRun(
-                flat_param, loss_out, use_mse, w_off, b_off, lr, max_defer,
-                self.ramp_first, self.ramp_growth)
-
-        def launch(xall, tall, B):
-            """One deferred-run launch: world-1 multistep, or the mesh
-            variant with an in-kernel all-reduce per step."""
-            self._launches += 1
-            if mesh is None:
-                ext_mod.toy_multistep(xall, tall, flat_param, loss_out,
-                                      use_mse, w_off, b_off, lr, B)
-            else:
-                ext_mod.toy_multistep_mesh(xall, tall, flat_param, loss_out,
-                                           use_mse, w_off, b_off, lr, B,
-                                           mesh)
-
-        if mesh is None:
-            eager = ToyFusedStep.step.__get__(self)
-        else:
-            def eager(x, t):  # single-step via the same mesh kernel (S=1):
-                # keeps the per-step collective order identical on all ranks
-                launch(x.contiguous(), t.contiguous(), x.shape[0])
-        x0 = t0 = None
-        shape = None
-        count = nx = nt = bk = bt = 0
-
-        def step(x: torch.Tensor, t: torch.Tensor) -> None:
-            nonlocal x0, t0, count, nx, nt, bk, bt, shape
-            if run is not None:
-                if run.pending:  # a native shard-bound run: order it
-                    flush_generic()
-                    run.launch_pending()  # an internal flush: does not arm
-            elif s_next != s_start:  # a shard-bound run is pending: order it
-                flush()
-            if count:
-                # fast path: the next contiguous slice of the pending run
-                if (x.data_ptr() == nx and t.data_ptr() == nt
-                        and x.shape == shape):
-                    count += 1
-                    nx += bk
-                    nt += bt
-                    if count >= max_defer:
-                        flush_generic()
-                    return
-                flush_generic()
-            if not (x.is_cuda and x.is_contiguous() and t.is_contiguous()):
-                eager(x, t)
-                return
-            x0, t0, count = x, t, 1
-            if run is not None:
-                # submitted before any later step_shard: the native run
-                # launches this one first (it cannot see it otherwise)
-                run.order_before(flush_generic)
-            shape = x.shape
-            bk = x.numel() * x.element_size()
-            bt = t.numel() * t.element_size()
-            nx = x.data_ptr() + bk
-            nt = t.data_ptr() + bt
-
-        def flush_generic() -> None:
-            nonlocal x0, t0, count
-            if count:
-                xx, tt, n = x0, t0, count
-                x0 = t0 = None
-                count = 0
-                if run is not None:
-                    run.order_before(None)
-                if n == 1:
-                    launch(xx, tt, xx.shape[0])  # S=1: bitwise == fused
-                else:
-                    B, K = xx.shape
-                    xall = xx.as_strided((n * B, K), (K, 1))
-                    tall = tt.as_strided((n * B,) + tt.shape[1:],
-                                         (tt.stride(0),) + tt.stride()[1:])
-                    launch(xall, tall, B)
-
-        self.step = step
-        if run is not None:
-            # a tensor-level run still pending was submitted first: it goes
-            # first here, as it does (order_before) ahead of a native launch
-            def flush() -> None:
-                flush_generic()
-                run.flush()  # launches what is pending and arms the ramp
-
-            def bind_shard(xs: torch.Tensor, ts: torch.Tensor,
-                           batch: int) -> None:
-                flush_generic()
-                run.bind_shard(xs, ts, batch)
-
-            self.flush = flush
-            self.bind_shard = bind_shard
-            self.step_shard = run.step_shard  # the C function itself
+        if x.is_cuda and x.is_contiguous() and t.is_contiguous():
+            run.step_tensors(x, t)
             return
-
-        # shard-bound path in Python (mesh, or no extension): bind the
-        # epoch shard once, then step by batch INDEX — no per-step
-        # tensor-view construction at all.
-        shard_x = shard_t = None
-        sbatch = 0
-        s_start = s_next = 0  # pending run = batch indices [s_start, s_next)
-
-        def bind_shard(xs: torch.Tensor, ts: torch.Tensor, batch: int) -> None:
-            nonlocal shard_x, shard_t, sbatch, s_start, s_next
-            flush()
-            assert xs.is_cuda and xs.is_contiguous() and ts.is_contiguous()
-            shard_x, shard_t, sbatch = xs, ts, batch
-            s_start = s_next = 0
-
-        def step_shard(i: int) -> None:
-            nonlocal s_start, s_next
-            if i == s_next:
-                s_next += 1
-                if s_next - s_start >= max_defer:
-                    flush()
-                return
-            flush()
-            s_start, s_next = i, i + 1
-
-        def flush() -> None:
-            nonlocal s_start, s_next
-            flush_generic()
-            if s_next > s_start:
-                lo, n = s_start * sbatch, (s_next - s_start) * sbatch
-                s_start = s_next
-                launch(shard_x[lo:lo + n], shard_t[lo:lo + n], sbatch)
-
-        self.flush = flush
-        self.bind_shard = bind_shard
-        self.step_shard = step_shard
+        run.launch_pending()  # submitted earlier: runs earlier (no arming)
+        if self._mesh is None:
+            super().step(x, t)
+        else:
+            # a single step through the same mesh kernel (S = 1): keeps the
+            # per-step collective order identical on all ranks
+            run.step_tensors(x.contiguous(), t.contiguous())
+            run.launch_pending()
 
 
 class GraphedAutogradStep:
@@ -464,26 +362,21 @@ class GraphedAutogradStep:
                            dtype=self._bdtype[0], device=self._bdev)
         tbuf = torch.empty((G * B,) + self._bshape[1][1:],
                            dtype=self._bdtype[1], device=self._bdev)
-        g = torch.cuda.CUDAGraph()
-        ctx = torch.cuda.graph(g)
-        try:
-            with ctx:
-                for i in range(G):
-                    self.loss = self._eager_step(xbuf[i * B:(i + 1) * B],
-                                                 tbuf[i * B:(i + 1) * B])
-            self._graphs[G] = (g, xbuf, tbuf)
-            return self._graphs[G]
-        except Exception as e:
-            import warnings
-            warnings.warn(
-                f"[mi355x_ddp] whole-step hipGraph capture failed ({e!r}); "
-                "GraphedAutogradStep running eager (correct, slower; no "
-                "further captures will be attempted in this process)",
-                RuntimeWarning, stacklevel=2)
+
+        def body():
+            for i in range(G):
+                self.loss = self._eager_step(xbuf[i * B:(i + 1) * B],
+                                             tbuf[i * B:(i + 1) * B])
+
+        g = _capture_graph(
+            body, "[mi355x_ddp] whole-step hipGraph capture failed ({e!r}); "
+            "GraphedAutogradStep running eager (correct, slower; no "
+            "further captures will be attempted in this process)")
+        if g is None:
             self._broken = True
-            _poison_captures(g)
-            _recover_failed_capture(ctx)
             return None
+        self._graphs[G] = (g, xbuf, tbuf)
+        return self._graphs[G]
 
     def _note_shapes(self, x, t):
         if self._bshape is None:
@@ -594,24 +487,11 @@ class GraphedToyStep(ToyFusedStep):
         # warm up collectives/kernels outside capture first
         super().step(self._x_static, self._t_static)
         torch.cuda.synchronize()
-        if _CAPTURE_POISONED:
-            self._graph = False  # earlier failed capture: stay eager
-            return
-        g = torch.cuda.CUDAGraph()
-        ctx = torch.cuda.graph(g)
-        try:
-            with ctx:
-                super().step(self._x_static, self._t_static)
-            self._graph = g
-        except Exception as e:  # capture unsupported -> eager fallback
-            import warnings
-            warnings.warn(
-                f"[mi355x_ddp] hipGraph capture failed ({e!r}); "
-                "GraphedToyStep running eager (correct, slower)",
-                RuntimeWarning, stacklevel=2)
-            self._graph = False
-            _poison_captures(g)
-            _recover_failed_capture(ctx)
+        g = _capture_graph(
+            lambda: ToyFusedStep.step(self, self._x_static, self._t_static),
+            "[mi355x_ddp] hipGraph capture failed ({e!r}); "
+            "GraphedToyStep running eager (correct, slower)")
+        self._graph = g if g is not None else False  # False: stay eager
 
     def step(self, x: torch.Tensor, t: torch.Tensor) -> None:
         if self._graph is None:

@@ -19,25 +19,48 @@ torch::Tensor linear_autograd(torch::Tensor x, torch::Tensor w,
 torch::Tensor mse_autograd(torch::Tensor y, torch::Tensor t);
 torch::Tensor ce_autograd(torch::Tensor y, torch::Tensor t);
 
-// The native shard-bound stepper of the world-1 persistent engine: the
-// shard_run.h tracker over toy_multistep_launch. bind_shard validates the
-// shard once and keeps raw pointers; step_shard(i) is then a few integer
-// operations, and a launch is pointer arithmetic plus the kernel dispatch.
-// The recorder variant has the same tracker and entry point but only notes
-// (first_step, n_steps) and touches no GPU API, so the schedule and the
+// The run tracker behind PersistentToyStep: shard_run.h's OrderedRuns over
+// the pointer-level launchers, toy_multistep_launch at world 1 and
+// toy_multistep_mesh_launch with a mesh. It defers two kinds of run, the
+// index run of the shard-bound protocol and the tensor run of step(x, t),
+// and OrderedRuns keeps them in submission order. Everything is validated
+// where a run STARTS (bind_shard; the first tensor of a tensor run), so a
+// launch is pointer arithmetic plus the kernel dispatch and cannot be
+// refused: with a mesh, no sequence range is taken for a launch that does
+// not happen. step_shard(i) is a few integer operations.
+// The recorder variant has the same trackers and entry points but only notes
+// its launches and touches no GPU API, so the schedule, the ordering and the
 // host-loop cost are testable without a GPU.
 class ToyShardRun : public std::enable_shared_from_this<ToyShardRun> {
- public:
-  using Tracker = ShardRun<std::function<void(int64_t, int64_t)>>;
+  struct Noted {
+    bool tensors;
+    int64_t first, n;  // first step, or the first span's x address
+  };
 
+ public:
+  using Runs = OrderedRuns<std::function<void(int64_t, int64_t)>,
+                           std::function<void(const Span&, int64_t)>>;
+
+  // With a mesh every rank must issue the same launches in the same order,
+  // so the schedule may depend on the submitted steps alone: no ramp, which
+  // starts at whichever flush a rank happens to make.
   ToyShardRun(torch::Tensor flat_param, torch::Tensor loss_out, bool use_mse,
               int64_t w_off, int64_t b_off, double lr, int64_t max_defer,
-              int64_t ramp_first, double growth)
+              int64_t ramp_first, double growth, P2pMesh* mesh)
       : param_(std::move(flat_param)), loss_(std::move(loss_out)),
-        use_mse_(use_mse), w_off_((int)w_off), b_off_((int)b_off),
-        lr_((float)lr),
-        run_([this](int64_t first, int64_t n) { launch(first, n); },
-             max_defer, ramp_first, growth) {
+        mesh_(mesh), use_mse_(use_mse), w_off_((int)w_off),
+        b_off_((int)b_off), lr_((float)lr),
+        runs_([this](int64_t first, int64_t n) {
+                const int64_t esz = bf16_ ? 2 : 4;
+                launch(xs_ + first * B_ * K_ * esz, ts_ + first * B_ * esz,
+                       B_, K_, n);
+              },
+              [this](const Span& f, int64_t n) {
+                launch(reinterpret_cast<const char*>(f.x),
+                       reinterpret_cast<const char*>(f.t), (int)f.rows,
+                       (int)f.cols, n);
+              },
+              max_defer, ramp_first, growth) {
     TORCH_CHECK(param_.is_cuda() && param_.is_contiguous(),
                 "ToyShardRun: flat_param must be a contiguous device tensor");
     const auto dt = param_.scalar_type();
@@ -52,17 +75,22 @@ class ToyShardRun : public std::enable_shared_from_this<ToyShardRun> {
     TORCH_CHECK(lossp_ == nullptr || (loss_.is_cuda() &&
                                       loss_.device() == param_.device()),
                 "ToyShardRun: loss_out must be on flat_param's device");
+    TORCH_CHECK(mesh_ == nullptr || ramp_first == 0,
+                "ToyShardRun: a mesh run takes no launch ramp (ramp_first 0)");
   }
 
   // recorder
   ToyShardRun(int64_t steps_bound, int64_t max_defer, int64_t ramp_first,
               double growth)
       : recorder_(true),
-        run_([this](int64_t first, int64_t n) {
-               recorded_.emplace_back(first, n);
-             },
-             max_defer, ramp_first, growth) {
-    run_.bind(steps_bound);
+        runs_([this](int64_t first, int64_t n) {
+                noted_.push_back({false, first, n});
+              },
+              [this](const Span& f, int64_t n) {
+                noted_.push_back({true, (int64_t)f.x, n});
+              },
+              max_defer, ramp_first, growth) {
+    runs_.bind(steps_bound);
   }
 
   ToyShardRun(const ToyShardRun&) = delete;
@@ -71,60 +99,96 @@ class ToyShardRun : public std::enable_shared_from_this<ToyShardRun> {
   void bind_shard(torch::Tensor xs, torch::Tensor ts, int64_t batch) {
     TORCH_CHECK(!recorder_, "a recorder binds step counts: use bind_steps");
     TORCH_CHECK(batch >= 1, "bind_shard: batch must be >= 1");
-    // the entry points' own validator (toy_kernels.hip), once per bind
-    const ToyDims d = toy_check_args("bind_shard", xs, ts, param_, nullptr,
-                                     false, loss_, w_off_, b_off_, batch);
-    run_.launch_pending();  // what is pending runs on the OLD shard
-    xs_ = std::move(xs);
-    ts_ = std::move(ts);
+    const ToyDims d = check("bind_shard", xs, ts, batch);
+    runs_.bind(d.S);  // what is pending runs first, on the OLD shard
+    shard_x_ = std::move(xs);
+    shard_t_ = std::move(ts);
+    xs_ = static_cast<const char*>(shard_x_.data_ptr());
+    ts_ = static_cast<const char*>(shard_t_.data_ptr());
     B_ = d.B;
     K_ = d.K;
-    run_.bind(d.S);
   }
 
   void bind_steps(int64_t steps_bound) {
     TORCH_CHECK(recorder_, "bind_steps is the recorder's bind");
-    run_.bind(steps_bound);
+    runs_.bind(steps_bound);
   }
 
-  // The engine's tensor-level step(x, t) path defers runs of its own. One
-  // still pending when this run launches was submitted FIRST, so it has to
-  // be launched first: `cb` (None clears) is called once, before the next
-  // launch from here.
-  void order_before(pybind11::object cb) {
-    before_launch_ = cb.is_none() ? pybind11::object() : std::move(cb);
+  // One step on the batch (x, t): it extends the pending tensor run when it
+  // is the next [rows, K] slice of the same buffers, else it is validated
+  // (the recorder only asks for contiguous tensors), what is pending is
+  // launched, and it starts a new run and is kept alive for it.
+  void step_tensors(torch::Tensor x, torch::Tensor t) {
+    TORCH_CHECK(x.is_contiguous() && t.is_contiguous(),
+                "step_tensors: x and t must be contiguous");
+    const Span s = span_of(x, t);
+    const bool extends = runs_.continues(s);
+    if (!extends && !recorder_ && check("step", x, t, -1).S == 0)
+      return;  // no rows
+    runs_.step_span(s);  // launches what is pending unless `s` extends it
+    if (!extends) {  // after that launch: it read the tensors let go here
+      first_x_ = std::move(x);
+      first_t_ = std::move(t);
+    }
   }
 
-  Tracker& tracker() { return run_; }
-  const std::vector<std::pair<int64_t, int64_t>>& recorded() const {
-    return recorded_;
+  Runs& runs() { return runs_; }
+  auto& tracker() { return runs_.index(); }
+
+  pybind11::list launches() const {
+    pybind11::list out;
+    for (const Noted& l : noted_)
+      out.append(l.tensors ? pybind11::make_tuple("t", l.first, l.n)
+                           : pybind11::make_tuple(l.first, l.n));
+    return out;
   }
 
  private:
-  void launch(int64_t first, int64_t n) {
-    // [first, first + n) lies inside the bound rows: step() admits no index
-    // at or past rows / batch
-    if (before_launch_) {
-      pybind11::object cb = std::move(before_launch_);
-      before_launch_ = pybind11::object();
-      cb();
-    }
-    const int64_t esz = bf16_ ? 2 : 4;
-    const char* xp = static_cast<const char*>(xs_.data_ptr());
-    const char* tp = static_cast<const char*>(ts_.data_ptr());
-    toy_multistep_launch(xp + first * B_ * K_ * esz, tp + first * B_ * esz,
-                         param_.data_ptr(), lossp_, use_mse_, w_off_, b_off_,
-                         lr_, B_, K_, (int)n, bf16_);
+  static Span span_of(const torch::Tensor& x, const torch::Tensor& t) {
+    Span s;
+    s.x = reinterpret_cast<uintptr_t>(x.data_ptr());
+    s.t = reinterpret_cast<uintptr_t>(t.data_ptr());
+    s.x_bytes = (int64_t)x.nbytes();
+    s.t_bytes = (int64_t)t.nbytes();
+    s.rows = x.dim() == 2 ? x.size(0) : -1;
+    s.cols = x.dim() == 2 ? x.size(1) : -1;
+    s.dtype = (int64_t)x.scalar_type() * 256 + (int64_t)t.scalar_type();
+    s.x_buf = x.storage().unsafeGetStorageImpl();
+    s.t_buf = t.storage().unsafeGetStorageImpl();
+    return s;
   }
 
-  torch::Tensor param_, loss_, xs_, ts_;
+  // the entry points' own validator (toy_kernels.hip), once per run
+  ToyDims check(const char* who, const torch::Tensor& x,
+                const torch::Tensor& t, int64_t batch) const {
+    const ToyDims d = toy_check_args(who, x, t, param_, nullptr, false, loss_,
+                                     w_off_, b_off_, batch);
+    if (mesh_ != nullptr) toy_check_mesh_args(who, d, *mesh_);
+    return d;
+  }
+
+  // n >= 1 steps of validated [B, K] tiles from x and t
+  void launch(const char* x, const char* t, int B, int K, int64_t n) {
+    if (mesh_ != nullptr)
+      toy_multistep_mesh_launch(x, t, param_.data_ptr(), lossp_, use_mse_,
+                                w_off_, b_off_, lr_, B, (int)n, bf16_, *mesh_);
+    else
+      toy_multistep_launch(x, t, param_.data_ptr(), lossp_, use_mse_, w_off_,
+                           b_off_, lr_, B, K, (int)n, bf16_);
+  }
+
+  torch::Tensor param_, loss_;
+  torch::Tensor shard_x_, shard_t_;  // the bound shard, kept alive
+  torch::Tensor first_x_, first_t_;  // the tensor run's first batch, likewise
+  P2pMesh* mesh_ = nullptr;          // not owned: the binding keeps it alive
+  const char* xs_ = nullptr;
+  const char* ts_ = nullptr;
   float* lossp_ = nullptr;
   bool use_mse_ = true, bf16_ = false, recorder_ = false;
   int w_off_ = 0, b_off_ = 0, B_ = 0, K_ = 0;
   float lr_ = 0.f;
-  std::vector<std::pair<int64_t, int64_t>> recorded_;
-  pybind11::object before_launch_;
-  Tracker run_;  // last: its launch callable uses the members above
+  std::vector<Noted> noted_;
+  Runs runs_;  // last: its launch callables use the members above
 };
 
 // step_shard as a bare METH_O C function whose self is a capsule owning a
@@ -270,15 +334,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("set_toy_multistep_chain_depth",
         &mi355x::set_toy_multistep_chain_depth, py::arg("depth"));
 
-  // Native shard-bound stepper (world-1 persistent engine). step_shard is a
-  // bare C function, fetched once and called per step; the rest is cold.
+  // The persistent engine's run tracker. step_shard is a bare C function,
+  // fetched once and called per step; the rest is cold.
   py::class_<mi355x::ToyShardRun, std::shared_ptr<mi355x::ToyShardRun>>(
       m, "ToyShardRun")
       .def(py::init<torch::Tensor, torch::Tensor, bool, int64_t, int64_t,
-                    double, int64_t, int64_t, double>(),
+                    double, int64_t, int64_t, double, mi355x::P2pMesh*>(),
            py::arg("flat_param"), py::arg("loss_out"), py::arg("use_mse"),
            py::arg("w_off"), py::arg("b_off"), py::arg("lr"),
-           py::arg("max_defer"), py::arg("ramp_first"), py::arg("growth"))
+           py::arg("max_defer"), py::arg("ramp_first"), py::arg("growth"),
+           py::arg("mesh") = nullptr,
+           // the run holds a non-owning P2pMesh*: keep the mesh alive with it
+           py::keep_alive<1, 11>())
       .def_static("recorder",
                   [](int64_t steps_bound, int64_t max_defer,
                      int64_t ramp_first, double growth) {
@@ -291,14 +358,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::arg("ts"), py::arg("batch"))
       .def("bind_steps", &mi355x::ToyShardRun::bind_steps,
            py::arg("steps_bound"))
-      .def("order_before", &mi355x::ToyShardRun::order_before, py::arg("cb"))
-      .def("flush", [](mi355x::ToyShardRun& r) { r.tracker().flush(); })
+      .def("step_tensors", &mi355x::ToyShardRun::step_tensors, py::arg("x"),
+           py::arg("t"))
+      .def("flush", [](mi355x::ToyShardRun& r) { r.runs().flush(); })
       .def("launch_pending",
-           [](mi355x::ToyShardRun& r) { r.tracker().launch_pending(); })
+           [](mi355x::ToyShardRun& r) { r.runs().launch_pending(); })
       .def_property_readonly("step_shard", &mi355x::shard_run_step_fn)
       .def_property_readonly(
           "launch_count",
-          [](mi355x::ToyShardRun& r) { return r.tracker().launch_count(); })
+          [](mi355x::ToyShardRun& r) { return r.runs().launch_count(); })
       .def_property_readonly(
           "max_defer",
           [](mi355x::ToyShardRun& r) { return r.tracker().max_defer(); })
@@ -306,14 +374,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "pending",
           [](mi355x::ToyShardRun& r) { return r.tracker().pending(); })
       .def_property_readonly(
+          "pending_tensors",
+          [](mi355x::ToyShardRun& r) { return r.runs().spans().pending(); })
+      .def_property_readonly(
           "threshold",
           [](mi355x::ToyShardRun& r) { return r.tracker().threshold(); })
-      .def_property_readonly("launches", [](mi355x::ToyShardRun& r) {
-        py::list out;
-        for (const auto& l : r.recorded())
-          out.append(py::make_tuple(l.first, l.second));
-        return out;
-      });
+      // the recorder's launches in order: (first_step, n_steps) of an index
+      // run, ("t", first x address, n_steps) of a tensor run
+      .def_property_readonly("launches", &mi355x::ToyShardRun::launches);
 
   py::class_<mi355x::P2pMesh>(m, "P2pMesh")
       .def(py::init<int, int, int>(), py::arg("rank"), py::arg("world"),

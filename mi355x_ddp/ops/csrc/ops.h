@@ -203,4 +203,18 @@ void toy_multistep_mesh(torch::Tensor x, torch::Tensor t,
                         bool use_mse, int64_t w_off, int64_t b_off, double lr,
                         int64_t batch, P2pMesh& mesh);
 
+// What the mesh kernels need beyond toy_check_args: a fast-path shape (batch
+// 32 or 64, K 20) and a connected mesh.
+void toy_check_mesh_args(const char* who, const ToyDims& d,
+                         const P2pMesh& mesh);
+// The launcher under toy_multistep_mesh, on raw device pointers, as
+// toy_multistep_launch is under toy_multistep (K is 20). The caller has
+// passed toy_check_args and toy_check_mesh_args, S >= 1, lr > 0: nothing
+// here can refuse the launch, so the S sequence numbers it takes from the
+// mesh are always used.
+void toy_multistep_mesh_launch(const void* x, const void* t, void* param,
+                               float* loss, bool use_mse, int w_off,
+                               int b_off, float lr, int B, int S, bool bf16,
+                               P2pMesh& mesh);
+
 }  // namespace mi355x

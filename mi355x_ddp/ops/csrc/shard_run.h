@@ -1,4 +1,6 @@
-// Run tracker and launch schedule of the shard-bound stepper.
+// Run trackers and launch schedule of the persistent engine: ShardRun (the
+// shard-bound stepper's index run, described here), SpanRun (the run of
+// step(x, t) tensors) and OrderedRuns (both, in submission order), below.
 //
 // A caller steps through a bound shard by batch INDEX. Consecutive indices
 // extend one pending run [s_start, s_next); the run is handed to
@@ -116,6 +118,138 @@ class ShardRun {
   int64_t steps_bound_ = 0;
   int64_t s_start_ = 0, s_next_ = 0;  // pending run [s_start_, s_next_)
   int64_t launch_count_ = 0;
+};
+
+// The tensor-level run: a caller that steps by (x, t) tensors instead of
+// indices. A span is one step's x and t as addresses; consecutive spans that
+// lie back to back in memory extend one pending run, handed to
+// launch(first_span, n_steps) when it reaches max_defer, when a span arrives
+// that does not extend it, and by launch_pending(). No ramp, never armed.
+struct Span {
+  uintptr_t x = 0, t = 0;            // addresses of the step's x and t
+  int64_t x_bytes = 0, t_bytes = 0;  // their sizes: the run's per-step strides
+  int64_t rows = 0, cols = 0;        // shape of x
+  int64_t dtype = 0;                 // opaque code of the element types
+  // Opaque identities of the buffers x and t lie in. Only the run's first
+  // span is kept alive by the caller, so a span of another buffer must not
+  // extend the run even where the two allocations happen to be adjacent.
+  const void* x_buf = nullptr;
+  const void* t_buf = nullptr;
+};
+
+template <typename Launch>
+class SpanRun {
+ public:
+  SpanRun(Launch launch, int64_t max_defer)
+      : launch_(std::move(launch)), max_defer_(max_defer) {
+    if (max_defer < 1) throw std::invalid_argument("max_defer must be >= 1");
+  }
+
+  // `s` starts exactly where the pending run ends, with the first span's
+  // shape and dtype, in the first span's buffers.
+  bool continues(const Span& s) const noexcept {
+    const Span& f = first_;
+    return count_ > 0 && s.x == f.x + (uintptr_t)(count_ * f.x_bytes) &&
+           s.t == f.t + (uintptr_t)(count_ * f.t_bytes) &&
+           s.x_bytes == f.x_bytes && s.t_bytes == f.t_bytes &&
+           s.rows == f.rows && s.cols == f.cols && s.dtype == f.dtype &&
+           s.x_buf == f.x_buf && s.t_buf == f.t_buf;
+  }
+
+  void step(const Span& s) {
+    if (!continues(s)) {
+      launch_pending();
+      first_ = s;
+    }
+    if (++count_ >= max_defer_) launch_pending();
+  }
+
+  void launch_pending() {
+    const int64_t n = count_;
+    if (n == 0) return;
+    count_ = 0;  // before the call: consistent if launch_ throws
+    ++launch_count_;
+    launch_(first_, n);
+  }
+
+  int64_t pending() const { return count_; }
+  int64_t launch_count() const { return launch_count_; }
+
+ private:
+  Launch launch_;
+  const int64_t max_defer_;
+  Span first_;
+  int64_t count_ = 0;
+  int64_t launch_count_ = 0;
+};
+
+// Both runs of one engine. Whatever the interleaving of index steps, spans,
+// binds and flushes, the steps execute in the order they were submitted:
+//   - at most one run of each kind is pending;
+//   - if both are pending, the span run is the older one. So a span launches
+//     a pending index run (and the span run before it) and starts a new run,
+//     and the index run's launch callable launches a pending span run first;
+//   - bind, launch_pending and flush launch the span run, then the index
+//     run; flush then arms the index run's ramp.
+// Index steps go to index() directly: a step that only extends the index
+// run touches nothing here.
+template <typename IndexLaunch, typename SpanLaunch>
+class OrderedRuns {
+  struct OlderFirst {
+    OrderedRuns* self;
+    void operator()(int64_t first, int64_t n) const {
+      self->spans_.launch_pending();
+      self->index_launch_(first, n);
+    }
+  };
+
+ public:
+  OrderedRuns(IndexLaunch index_launch, SpanLaunch span_launch,
+              int64_t max_defer, int64_t ramp_first, double growth)
+      : index_launch_(std::move(index_launch)),
+        spans_(std::move(span_launch), max_defer),
+        index_(OlderFirst{this}, max_defer, ramp_first, growth) {}
+  OrderedRuns(const OrderedRuns&) = delete;  // index_ points back here
+  OrderedRuns& operator=(const OrderedRuns&) = delete;
+
+  ShardRun<OlderFirst>& index() { return index_; }
+  const SpanRun<SpanLaunch>& spans() const { return spans_; }
+
+  // `s` would only extend the pending span run: nothing gets launched, so a
+  // caller has nothing to validate or to keep alive for it.
+  bool continues(const Span& s) const noexcept {
+    return index_.pending() == 0 && spans_.continues(s);
+  }
+
+  void step_span(const Span& s) {
+    if (!continues(s)) launch_pending();
+    spans_.step(s);
+  }
+
+  void bind(int64_t steps_bound) {
+    if (steps_bound < 0) throw std::invalid_argument("steps_bound < 0");
+    launch_pending();
+    index_.bind(steps_bound);
+  }
+
+  void launch_pending() {
+    spans_.launch_pending();
+    index_.launch_pending();
+  }
+
+  void flush() {
+    spans_.launch_pending();
+    index_.flush();
+  }
+
+  int64_t launch_count() const {
+    return index_.launch_count() + spans_.launch_count();
+  }
+
+ private:
+  IndexLaunch index_launch_;
+  SpanRun<SpanLaunch> spans_;
+  ShardRun<OlderFirst> index_;
 };
 
 }  // namespace mi355x

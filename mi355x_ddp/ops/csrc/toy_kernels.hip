@@ -1616,26 +1616,21 @@ void toy_multistep(torch::Tensor x, torch::Tensor t, torch::Tensor param_flat,
                        x.scalar_type() == at::kBFloat16);
 }
 
-void toy_multistep_mesh(torch::Tensor x, torch::Tensor t,
-                        torch::Tensor param_flat, torch::Tensor loss_out,
-                        bool use_mse, int64_t w_off, int64_t b_off, double lr,
-                        int64_t batch, P2pMesh& mesh) {
-  // everything is checked before the mesh is touched: a sequence range
-  // taken for a launch that never happens would desynchronise the ranks
-  TORCH_CHECK(batch >= 1, "toy_multistep_mesh: batch must be >= 1");
-  const ToyDims d = toy_check_args("toy_multistep_mesh", x, t, param_flat,
-                                   nullptr, false, loss_out, w_off, b_off,
-                                   batch);
-  const int B = d.B, S = d.S;
-  TORCH_CHECK((B == 32 || B == 64) && d.K == 20,
-              "mesh multistep supports the fast-path shapes "
+void toy_check_mesh_args(const char* who, const ToyDims& d,
+                         const P2pMesh& mesh) {
+  TORCH_CHECK((d.B == 32 || d.B == 64) && d.K == 20, who,
+              ": mesh multistep supports the fast-path shapes "
               "(batch 32 or 64, K 20)");
-  TORCH_CHECK((float)lr > 0.f,
-              "mesh multistep applies SGD in-kernel: lr must be > 0");
-  TORCH_CHECK(mesh.connected(),
-              "toy_multistep_mesh: the mesh is not connected");
-  if (S == 0) return;
-  float* lossp = loss_ptr(loss_out);
+  TORCH_CHECK(mesh.connected(), who, ": the mesh is not connected");
+}
+
+void toy_multistep_mesh_launch(const void* x, const void* t, void* param,
+                               float* loss, bool use_mse, int w_off,
+                               int b_off, float lr, int B, int S, bool bf16,
+                               P2pMesh& mesh) {
+  // the sequence range is taken here, where nothing can refuse the launch
+  // any more: one taken for a launch that never happens would desynchronise
+  // the ranks
   const MeshArgs m{mesh.peer_slots(), mesh.my_mb(), mesh.world(),
                    1.f / (float)mesh.world(),
                    mesh.alloc_seq((unsigned long long)S), mesh.err_flag()};
@@ -1643,13 +1638,32 @@ void toy_multistep_mesh(torch::Tensor x, torch::Tensor t,
     using T = decltype(zero);
     with_fast_batch(B, [&](auto b) {
       launch_toy_multistep_mfma<T, decltype(b)::value, true>(
-          cdptr<T>(x), cdptr<T>(t), dptr<T>(param_flat), lossp, use_mse,
-          (int)w_off, (int)b_off, (float)lr, S, m);
+          static_cast<const T*>(x), static_cast<const T*>(t),
+          static_cast<T*>(param), loss, use_mse, w_off, b_off, lr, S, m);
     });
   };
-  if (x.scalar_type() == at::kFloat) go(float{});
+  if (!bf16) go(float{});
   else go(__hip_bfloat16{});
   HIP_OK(hipGetLastError());
+}
+
+void toy_multistep_mesh(torch::Tensor x, torch::Tensor t,
+                        torch::Tensor param_flat, torch::Tensor loss_out,
+                        bool use_mse, int64_t w_off, int64_t b_off, double lr,
+                        int64_t batch, P2pMesh& mesh) {
+  // everything is checked before the mesh is touched
+  TORCH_CHECK(batch >= 1, "toy_multistep_mesh: batch must be >= 1");
+  const ToyDims d = toy_check_args("toy_multistep_mesh", x, t, param_flat,
+                                   nullptr, false, loss_out, w_off, b_off,
+                                   batch);
+  TORCH_CHECK((float)lr > 0.f,
+              "mesh multistep applies SGD in-kernel: lr must be > 0");
+  toy_check_mesh_args("toy_multistep_mesh", d, mesh);
+  if (d.S == 0) return;
+  toy_multistep_mesh_launch(x.data_ptr(), t.data_ptr(), param_flat.data_ptr(),
+                            loss_ptr(loss_out), use_mse, (int)w_off,
+                            (int)b_off, (float)lr, d.B, d.S,
+                            x.scalar_type() == at::kBFloat16, mesh);
 }
 
 template <typename T>

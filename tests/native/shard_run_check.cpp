@@ -222,9 +222,238 @@ static void randomized(uint64_t seed) {
                  (unsigned long long)seed, got.size(), want.size());
 }
 
+// -- the tensor-level run ---------------------------------------------------
+using mi355x::Span;
+using SpanLaunches = std::vector<std::pair<Span, int64_t>>;
+using Spans = mi355x::SpanRun<std::function<void(const Span&, int64_t)>>;
+
+// Two pretend buffers per operand, adjacent in address: buffer 1 starts at
+// the byte where buffer 0 ends. Only the identity tells them apart.
+static const char kBufId[4] = {};
+static constexpr uintptr_t kXBase = 0x100000, kTBase = 0x900000;
+static constexpr int64_t kBufSteps = 64;  // steps of the widest shape
+
+// a [rows, 8] f32 step of buffer `buf` at the given addresses
+static Span span_at(int buf, int64_t rows, uintptr_t x, uintptr_t t) {
+  Span s;
+  s.x = x;
+  s.t = t;
+  s.x_bytes = rows * 8 * 4;
+  s.t_bytes = rows * 4;
+  s.rows = rows;
+  s.cols = 8;
+  s.dtype = 7;
+  s.x_buf = &kBufId[buf];
+  s.t_buf = &kBufId[2 + buf];
+  return s;
+}
+
+static bool same_span(const Span& a, const Span& b) {
+  return a.x == b.x && a.t == b.t && a.x_bytes == b.x_bytes &&
+         a.t_bytes == b.t_bytes && a.rows == b.rows && a.cols == b.cols &&
+         a.dtype == b.dtype && a.x_buf == b.x_buf && a.t_buf == b.t_buf;
+}
+
+// step k of a launched run, as the kernel will address it
+static Span kth(const Span& first, int64_t k) {
+  Span s = first;
+  s.x += (uintptr_t)(k * first.x_bytes);
+  s.t += (uintptr_t)(k * first.t_bytes);
+  return s;
+}
+
+static void adjacent_buffers_do_not_merge() {
+  SpanLaunches rec;
+  Spans r([&rec](const Span& f, int64_t n) { rec.emplace_back(f, n); }, 16);
+  const int64_t rows = 4;
+  const Span last0 = span_at(0, rows, kXBase + 10 * rows * 32,
+                             kTBase + 10 * rows * 4);
+  // buffer 1 begins exactly where that span ends, in x and in t
+  const Span first1 = span_at(1, rows, last0.x + (uintptr_t)last0.x_bytes,
+                              last0.t + (uintptr_t)last0.t_bytes);
+  r.step(last0);
+  CHECK(!r.continues(first1));
+  r.step(first1);
+  r.launch_pending();
+  CHECK(rec.size() == 2 && rec[0].second == 1 && rec[1].second == 1);
+  CHECK(r.launch_count() == 2);
+  // the same addresses in ONE buffer do merge
+  rec.clear();
+  Span same = first1;
+  same.x_buf = last0.x_buf;
+  same.t_buf = last0.t_buf;
+  r.step(last0);
+  CHECK(r.continues(same));
+  r.step(same);
+  r.launch_pending();
+  CHECK(rec.size() == 1 && rec[0].second == 2);
+  // x in the same buffer, t in another: no merge either
+  rec.clear();
+  same.t_buf = first1.t_buf;
+  r.step(last0);
+  r.step(same);
+  r.launch_pending();
+  CHECK(rec.size() == 2);
+}
+
+// Naive model of the span run: the submitted spans in order, with a cut
+// mark where a launch boundary is due (a span that does not continue the
+// one before it, max_defer reached, a flush). The tracker must launch
+// exactly those groups.
+static void randomized_spans(uint64_t seed) {
+  std::mt19937_64 rng(seed);
+  auto pick = [&rng](int64_t lo, int64_t hi) {
+    return std::uniform_int_distribution<int64_t>(lo, hi)(rng);
+  };
+  const int64_t max_defer = pick(1, 12);
+  SpanLaunches rec;
+  Spans r([&rec](const Span& f, int64_t n) { rec.emplace_back(f, n); },
+          max_defer);
+
+  std::vector<Span> want;           // every submitted span
+  std::vector<int64_t> want_sizes;  // the groups they must be launched in
+  int64_t group = 0;                // spans of the group being built
+  auto cut = [&] {
+    if (group) want_sizes.push_back(group);
+    group = 0;
+  };
+  int buf = 0;
+  int64_t rows = 4;
+  uintptr_t x = kXBase, t = kTBase;  // where the next contiguous span starts
+  for (int op = 0; op < 400; ++op) {
+    const int64_t what = pick(0, 99);
+    if (what < 6) {  // flush
+      r.launch_pending();
+      CHECK(r.pending() == 0);
+      cut();
+      continue;
+    }
+    bool contiguous = true;
+    if (what < 14) {  // a gap: skip one step
+      x += (uintptr_t)(rows * 32);
+      t += (uintptr_t)(rows * 4);
+      contiguous = false;
+    } else if (what < 22) {  // another shape at the contiguous address
+      rows = rows == 4 ? 2 : 4;
+      contiguous = false;
+    } else if (what < 28) {  // the other buffer, at its first byte
+      buf ^= 1;
+      x = kXBase + (uintptr_t)(buf * kBufSteps * 4 * 32);
+      t = kTBase + (uintptr_t)(buf * kBufSteps * 4 * 4);
+      contiguous = false;
+    } else if (what < 32) {  // a gap in t only
+      t += (uintptr_t)(rows * 4);
+      contiguous = false;
+    }
+    const Span s = span_at(buf, rows, x, t);
+    CHECK(r.continues(s) == (contiguous && group > 0));
+    if (!contiguous) cut();
+    r.step(s);
+    want.push_back(s);
+    if (++group >= max_defer) cut();
+    CHECK(r.pending() == group);
+    x += (uintptr_t)s.x_bytes;
+    t += (uintptr_t)s.t_bytes;
+  }
+  r.launch_pending();
+  cut();
+  std::vector<int64_t> got_sizes;
+  std::vector<Span> got;
+  for (const auto& l : rec) {
+    got_sizes.push_back(l.second);
+    for (int64_t k = 0; k < l.second; ++k) got.push_back(kth(l.first, k));
+  }
+  CHECK(got_sizes == want_sizes);
+  CHECK(r.launch_count() == (int64_t)rec.size());
+  CHECK(got.size() == want.size());
+  for (size_t k = 0; k < got.size() && k < want.size(); ++k)
+    CHECK(same_span(got[k], want[k]));
+}
+
+// The ordering rule of OrderedRuns: over random interleavings of index
+// steps, spans, binds and flushes, the launch stream expanded to steps is
+// the submission order.
+static void randomized_ordering(uint64_t seed) {
+  std::mt19937_64 rng(seed);
+  auto pick = [&rng](int64_t lo, int64_t hi) {
+    return std::uniform_int_distribution<int64_t>(lo, hi)(rng);
+  };
+  const int64_t max_defer = pick(1, 20);
+  const int64_t ramp_first = pick(0, 6);
+  // a step: (bind number, index) of an index step, (-1, x address) of a span
+  std::vector<std::pair<int64_t, int64_t>> want, got;
+  int64_t bind_no = 0, bound = 0;
+  bool ok = true;
+  using Runs = mi355x::OrderedRuns<std::function<void(int64_t, int64_t)>,
+                                   std::function<void(const Span&, int64_t)>>;
+  Runs runs(
+      [&](int64_t first, int64_t n) {
+        if (n < 1 || n > max_defer || first < 0 || first + n > bound)
+          ok = false;
+        for (int64_t i = first; i < first + n; ++i)
+          got.emplace_back(bind_no, i);
+      },
+      [&](const Span& f, int64_t n) {
+        if (n < 1 || n > max_defer) ok = false;
+        for (int64_t k = 0; k < n; ++k)
+          got.emplace_back(-1, (int64_t)kth(f, k).x);
+      },
+      max_defer, ramp_first, 2.0);
+
+  int64_t next = 0;
+  uintptr_t x = kXBase, t = kTBase;
+  for (int op = 0; op < 500; ++op) {
+    const int64_t what = pick(0, 99);
+    if (what < 4 || bound == 0) {
+      const int64_t nb = pick(1, 50);
+      runs.bind(nb);  // the launches it makes still belong to the old bind
+      ++bind_no;
+      bound = nb;
+      next = 0;
+      CHECK(runs.index().pending() == 0 && runs.spans().pending() == 0);
+    } else if (what < 9) {
+      runs.flush();
+      CHECK(runs.index().pending() == 0 && runs.spans().pending() == 0);
+    } else if (what < 12) {
+      runs.launch_pending();
+      CHECK(runs.index().pending() == 0 && runs.spans().pending() == 0);
+    } else if (what < 55) {  // index step, now and then a jump
+      int64_t i = what < 18 ? pick(0, bound - 1) : next;
+      if (i >= bound) i = 0;
+      if (pick(0, 1) == 0 || !runs.index().extend(i)) runs.index().step(i);
+      want.emplace_back(bind_no, i);
+      next = i + 1;
+    } else {  // span, now and then after a gap
+      if (what < 62) {
+        x += 128;
+        t += 16;
+      }
+      const Span s = span_at(0, 4, x, t);
+      const bool extends = runs.continues(s);
+      const int64_t before = runs.spans().pending();
+      runs.step_span(s);
+      if (extends) CHECK(runs.spans().pending() == (before + 1) % max_defer);
+      want.emplace_back(-1, (int64_t)s.x);
+      x += (uintptr_t)s.x_bytes;
+      t += (uintptr_t)s.t_bytes;
+    }
+  }
+  runs.flush();
+  CHECK(ok);
+  CHECK(got == want);
+  CHECK(runs.launch_count() ==
+        runs.index().launch_count() + runs.spans().launch_count());
+  if (got != want)
+    std::fprintf(stderr, "ordering seed %llu: executed %zu steps of %zu\n",
+                 (unsigned long long)seed, got.size(), want.size());
+}
+
 int main() {
   schedules();
   for (uint64_t seed = 1; seed <= 300; ++seed) randomized(seed);
+  adjacent_buffers_do_not_merge();
+  for (uint64_t seed = 1; seed <= 200; ++seed) randomized_spans(seed);
+  for (uint64_t seed = 1; seed <= 200; ++seed) randomized_ordering(seed);
   if (g_failures) {
     std::fprintf(stderr, "%d check(s) failed\n", g_failures);
     return 1;

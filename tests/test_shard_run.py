@@ -172,6 +172,152 @@ def test_bad_constructor_arguments():
     _rec(ramp_first=0, growth=1.0)  # growth is unused without a ramp
 
 
+# -- the mesh schedule, and the tensor-level run ---------------------------
+def test_unramped_schedule_equals_the_closure_tracker_it_replaced():
+    """With a mesh the engine runs this tracker with ramp_first = 0 where it
+    ran a Python closure tracker before. Every rank must keep issuing the
+    same launches, so the two must cut any in-range sequence of steps, binds
+    and flushes into the same launches. max_defer >= 2: at 1 the closure
+    launched a restarted run only with its second step, (5, 2) for steps
+    5, 6, which a max_defer of 1 does not allow."""
+    import random
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from bench_host_loop import closure_engine
+
+    rng = random.Random(20)
+    for trial in range(150):
+        md = rng.choice([2, 3, 5, 16, 64])
+        bound = rng.randrange(1, 80)
+        run = _rec(steps_bound=bound, max_defer=md, ramp_first=0)
+        bind, step, flush, want = closure_engine(md)
+        nxt = 0
+        for _ in range(rng.randrange(1, 300)):
+            r = rng.random()
+            if r < 0.03:
+                bound = rng.randrange(1, 80)
+                run.bind_steps(bound)
+                bind(None, None, 32)
+                nxt = 0
+            elif r < 0.08:
+                run.flush()
+                flush()
+            else:
+                i = nxt if r > 0.2 and nxt < bound else rng.randrange(bound)
+                run.step_shard(i)
+                step(i)
+                nxt = i + 1
+        run.flush()
+        flush()
+        assert run.launches == want, (trial, md)
+        assert run.launch_count == len(want)
+
+
+def _tiles(n=48, rows=4, cols=3):
+    import torch
+    X = torch.zeros(n * rows, cols)
+    T = torch.zeros(n * rows, 1)
+    return [(X[i * rows:(i + 1) * rows], T[i * rows:(i + 1) * rows])
+            for i in range(n)]
+
+
+def _expand(launches, x_bytes):
+    """The recorded launches as steps: ("s", index) and ("t", x address)."""
+    out = []
+    for l in launches:
+        if l[0] == "t":
+            out += [("t", l[1] + k * x_bytes) for k in range(l[2])]
+        else:
+            out += [("s", i) for i in range(l[0], l[0] + l[1])]
+    return out
+
+
+def test_tensor_run_merges_contiguous_tiles_up_to_max_defer():
+    tiles = _tiles()
+    run = _rec(max_defer=16)
+    for x, t in tiles[:40]:
+        run.step_tensors(x, t)
+    assert run.pending_tensors == 8 and run.pending == 0
+    run.step_tensors(*tiles[41])          # a gap: launches the 8
+    assert run.pending_tensors == 1
+    run.flush()
+    a = tiles[0][0].data_ptr()
+    nb = tiles[0][0].numel() * 4
+    assert run.launches == [("t", a, 16), ("t", a + 16 * nb, 16),
+                            ("t", a + 32 * nb, 8), ("t", a + 41 * nb, 1)]
+    assert run.launch_count == 4
+    # a flush does not arm the tensor run: it has no ramp
+    for x, t in tiles[:20]:
+        run.step_tensors(x, t)
+    run.flush()
+    assert _sizes_t(run, 4) == [16, 4]
+
+
+def _sizes_t(run, since):
+    return [l[2] for l in run.launches[since:]]
+
+
+def test_tensor_run_does_not_cross_storages_shapes_or_dtypes():
+    import torch
+    (x0, t0), (x1, t1) = _tiles()[:2]
+    other_x, other_t = _tiles()[1]        # same shapes, storages of its own
+    run = _rec()
+    run.step_tensors(x0, t0)
+    run.step_tensors(other_x, other_t)
+    run.step_tensors(x0, t0)
+    run.step_tensors(x1, other_t)         # x continues, t does not
+    run.step_tensors(x0, t0)
+    run.step_tensors(x1.view(2, 6), t1)   # the next bytes, another shape
+    run.step_tensors(x0, t0)
+    run.step_tensors(x1.view(torch.int32), t1)
+    run.flush()
+    assert _sizes_t(run, 0) == [1] * 8
+    run.step_tensors(x0, t0)
+    run.step_tensors(x1, t1)
+    run.flush()
+    assert _sizes_t(run, 8) == [2]
+
+
+def test_tensor_and_index_steps_execute_in_submission_order():
+    import random
+    tiles = _tiles()
+    x_bytes = tiles[0][0].numel() * 4
+    rng = random.Random(5)
+    for trial in range(60):
+        md = rng.choice([1, 2, 7, 16])
+        run = _rec(steps_bound=64, max_defer=md,
+                   ramp_first=rng.choice([0, 2]))
+        step = run.step_shard
+        want, nxt, nxt_tile = [], 0, 0
+        for _ in range(200):
+            r = rng.random()
+            if r < 0.45:
+                i = nxt if r > 0.08 and nxt < 64 else rng.randrange(64)
+                step(i)
+                want.append(("s", i))
+                nxt = i + 1
+            elif r < 0.9:
+                j = (nxt_tile if r > 0.53 and nxt_tile < len(tiles)
+                     else rng.randrange(len(tiles)))
+                run.step_tensors(*tiles[j])
+                want.append(("t", tiles[j][0].data_ptr()))
+                nxt_tile = j + 1
+            elif r < 0.95:
+                run.flush()
+                assert run.pending == 0 and run.pending_tensors == 0
+            else:
+                # the same bound: the launches' indices keep their meaning
+                run.bind_steps(64)
+                nxt = 0
+            # both pending: the tensor run is the older one, so a tensor
+            # step never leaves index steps pending behind it
+            if want and want[-1][0] == "t":
+                assert run.pending == 0
+        run.flush()
+        assert _expand(run.launches, x_bytes) == want, (trial, md)
+        assert all(l[-1] <= md for l in run.launches)
+        assert run.launch_count == len(run.launches)
+
+
 # -- through bench.drive_shard_bound, as the benchmark drives it ----------
 class _Data:
     def __init__(self):

@@ -44,8 +44,9 @@ class _Data:
 
 
 def closure_engine(max_defer):
-    """The pre-native tracker of PersistentToyStep._install_fast_path:
-    closures over nonlocal counters; a launch only counts."""
+    """The tracker PersistentToyStep had before the native stepper:
+    closures over nonlocal counters; a launch only counts. Also the oracle
+    of the unramped schedule in tests/test_shard_run.py."""
     launches = []
     s_start = s_next = 0
 
