@@ -92,6 +92,34 @@ def linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None):
 
 
 # ---------------------------------------------------------------------------
+# Fused short-sequence self-attention (csrc/attention_kernels.hip)
+# ---------------------------------------------------------------------------
+def self_attention(qkv: torch.Tensor, heads: int) -> torch.Tensor:
+    """softmax(Q K^T / sqrt(D)) V per head, on the packed in-projection
+    output: `qkv` is [B, N, 3*E] with columns [0,E) Q, [E,2E) K, [2E,3E) V
+    and head h at columns h*D.. of each (E = heads*D); the result is
+    [B, N, E], ready for the out-projection. No mask, no dropout.
+
+    On the GPU one workgroup per (batch, head) runs the whole head out of
+    LDS, forward and backward (1 <= N <= 64, D in 16/32/64, fp32 or bf16
+    storage, fp32 arithmetic); other shapes raise. Under autocast the input
+    is cast to the autocast dtype, as `linear` does. The CPU path is the
+    formula in plain torch ops, the kernels' mirror."""
+    if qkv.is_cuda:
+        if torch.is_autocast_enabled("cuda"):
+            qkv = qkv.to(torch.get_autocast_dtype("cuda"))
+        return ext().attention_autograd(qkv, heads)
+    B, N, E3 = qkv.shape
+    if heads < 1 or E3 % (3 * heads):
+        raise ValueError("self_attention: the last dimension must be "
+                         "3 * heads * D")
+    D = E3 // (3 * heads)
+    q, k, v = qkv.view(B, N, 3, heads, D).permute(2, 0, 3, 1, 4)
+    p = torch.softmax(q @ k.transpose(-1, -2) * D ** -0.5, dim=-1)
+    return (p @ v).transpose(1, 2).reshape(B, N, heads * D)
+
+
+# ---------------------------------------------------------------------------
 # Losses (reference: CE at single_gpu.py:24, MSE at multinode_torchrun.py:46;
 # both take float probability/value targets of the same shape as the output)
 # ---------------------------------------------------------------------------

@@ -115,6 +115,25 @@ struct CeFn : public torch::autograd::Function<CeFn> {
   }
 };
 
+// Fused self-attention on the packed in-projection output. Saved for the
+// backward: qkv and the forward's row statistics, nothing else.
+struct AttnFn : public torch::autograd::Function<AttnFn> {
+  static torch::Tensor forward(AutogradContext* ctx, torch::Tensor qkv,
+                               int64_t heads) {
+    auto outs = attn_fwd(qkv, heads);  // (out, row_stats)
+    ctx->save_for_backward({qkv, outs[1]});
+    ctx->saved_data["heads"] = heads;
+    return outs[0];
+  }
+
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    auto saved = ctx->get_saved_variables();
+    return {attn_bwd(grads[0].contiguous(), saved[0], saved[1],
+                     ctx->saved_data["heads"].toInt()),
+            torch::Tensor()};
+  }
+};
+
 }  // namespace
 
 torch::Tensor linear_autograd(torch::Tensor x, torch::Tensor w,
@@ -128,6 +147,10 @@ torch::Tensor mse_autograd(torch::Tensor y, torch::Tensor t) {
 
 torch::Tensor ce_autograd(torch::Tensor y, torch::Tensor t) {
   return CeFn::apply(y, t);
+}
+
+torch::Tensor attention_autograd(torch::Tensor qkv, int64_t heads) {
+  return AttnFn::apply(qkv, heads);
 }
 
 }  // namespace mi355x

@@ -18,6 +18,7 @@ torch::Tensor linear_autograd(torch::Tensor x, torch::Tensor w,
                               c10::optional<torch::Tensor> b);
 torch::Tensor mse_autograd(torch::Tensor y, torch::Tensor t);
 torch::Tensor ce_autograd(torch::Tensor y, torch::Tensor t);
+torch::Tensor attention_autograd(torch::Tensor qkv, int64_t heads);
 
 // The run tracker behind PersistentToyStep: shard_run.h's OrderedRuns over
 // the pointer-level launchers, toy_multistep_launch at world 1 and
@@ -271,6 +272,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dy"), py::arg("dw"), py::arg("db"),
         py::arg("accumulate") = false);
   m.def("linear_bwd_input", &mi355x::linear_bwd_input);
+  m.def("attn_fwd", &mi355x::attn_fwd, py::arg("qkv"), py::arg("heads"),
+        py::arg("out") = c10::nullopt, py::arg("row_stats") = c10::nullopt);
+  m.def("attn_bwd", &mi355x::attn_bwd, py::arg("dout"), py::arg("qkv"),
+        py::arg("row_stats"), py::arg("heads"),
+        py::arg("dqkv") = c10::nullopt);
   m.def("gemm_bf16", &mi355x::gemm_bf16, py::arg("x"), py::arg("w"),
         py::arg("bias") = c10::nullopt);
   m.def("ce_fwd", &mi355x::ce_fwd);
@@ -403,6 +409,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("w"), py::arg("bias") = c10::nullopt);
   m.def("mse_autograd", &mi355x::mse_autograd);
   m.def("ce_autograd", &mi355x::ce_autograd);
+  m.def("attention_autograd", &mi355x::attention_autograd, py::arg("qkv"),
+        py::arg("heads"));
 
   py::class_<mi355x::ReducerCore, std::shared_ptr<mi355x::ReducerCore>>(
       m, "ReducerCore")

@@ -1,7 +1,8 @@
 // Host-side launcher declarations for the MI355X (gfx950) kernel pack.
 // Implementations in kernels.hip, for the toy training-step family
 // (toy_fused_fwd_bwd, toy_multistep*) toy_kernels.hip, and for the
-// flat-bucket optimizers optim_kernels.hip; bound to Python in bindings.hip.
+// flat-bucket optimizers optim_kernels.hip, for the fused self-attention
+// attention_kernels.hip; bound to Python in bindings.hip.
 #pragma once
 #include <torch/extension.h>
 #include <cstdint>
@@ -31,6 +32,25 @@ torch::Tensor linear_bwd_input(torch::Tensor dy, torch::Tensor w);
 // y = x @ w^T + bias. No model path routes to it; it is tested and timed.
 torch::Tensor gemm_bf16(torch::Tensor x, torch::Tensor w,
                         c10::optional<torch::Tensor> bias);
+
+// Fused short-sequence self-attention over the packed in-projection output
+// (attention_kernels.hip): qkv [B, N, 3*E] contiguous f32/bf16, columns
+// [0,E) Q, [E,2E) K, [2E,3E) V, head h at columns h*D.. of each, E = heads*D.
+// 1 <= N <= 64, D in {16, 32, 64}, scale 1/sqrt(D), no mask, no dropout;
+// anything else is refused before a launch, and B == 0 launches nothing.
+// attn_fwd returns (out [B, N, E], row_stats f32 [B, heads, N, 2]: the max of
+// a row's raw scores and the reciprocal of its sum of exponentials).
+// attn_bwd returns dqkv [B, N, 3*E] in qkv's layout from dout [B, N, E]. It
+// takes delta = rowsum(dO * O) as rowsum(P * dP) from its own registers, so
+// the forward's `out` is neither read nor kept for it. Results may be
+// preallocated (contiguous, 16-byte aligned, of the shapes above).
+std::vector<torch::Tensor> attn_fwd(
+    torch::Tensor qkv, int64_t heads,
+    c10::optional<torch::Tensor> out = c10::nullopt,
+    c10::optional<torch::Tensor> row_stats = c10::nullopt);
+torch::Tensor attn_bwd(torch::Tensor dout, torch::Tensor qkv,
+                       torch::Tensor row_stats, int64_t heads,
+                       c10::optional<torch::Tensor> dqkv = c10::nullopt);
 
 // Cross-entropy with class-probability targets (C may be 1: the reference's
 // degenerate Linear(20,1) case, single_gpu.py:24 + utils.py:7).

@@ -1,6 +1,7 @@
 """Time ViT-L/32 training steps through the native engine (multi-bucket
 reducer + fused SGD; the model the reference imports but leaves commented
-out — multigpu_profile.py:24). MI355X_AUTOCAST_BF16=1 for bf16."""
+out — multigpu_profile.py:24). MI355X_AUTOCAST_BF16=1 for bf16,
+MI355X_VIT_ATTENTION=hip for the fused short-sequence attention kernels."""
 import os
 import sys
 import time
@@ -17,7 +18,8 @@ steps = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 bf16 = os.environ.get("MI355X_AUTOCAST_BF16") == "1"
 torch.manual_seed(0)
 dev = "cuda:0"
-model = vit_l_32().to(dev)
+attention = os.environ.get("MI355X_VIT_ATTENTION", "torch")
+model = vit_l_32(attention=attention).to(dev)
 x = torch.rand(32, 3, 224, 224, device=dev)
 t = torch.rand(32, 1000, device=dev)
 params = list(model.parameters())
@@ -44,6 +46,7 @@ one(5)
 t0 = time.perf_counter()
 loss = one(steps)
 dt = (time.perf_counter() - t0) / steps
-print(f"vit_l_32 bs32 {'bf16' if bf16 else 'fp32'}: {dt*1e3:.2f} ms/step "
+print(f"vit_l_32 bs32 {'bf16' if bf16 else 'fp32'} attention={attention}: "
+      f"{dt*1e3:.2f} ms/step "
       f"({32/dt:.0f} img/s) buckets={len(reducer.buckets)} "
       f"loss={float(loss.detach()):.4f}")
