@@ -9,12 +9,15 @@ hidden 1024, MLP 4096, 16 heads, learned position embeddings, pre-norm
 encoder blocks, class token head) so the parameter census and DDP
 gradient payload (~305 M params, ~1.2 GB fp32 grads) are the real thing.
 
-LayerNorm/GELU run through PyTorch-ROCm (MIOpen/rocBLAS — the same
-scoping as ResNet's convs); the classifier head uses the
-hand-written MFMA linear. Attention is `attention="torch"`
+GELU runs through PyTorch-ROCm (the same scoping as ResNet's convs, SURVEY
+§2.2 N11); the classifier head uses the hand-written MFMA linear. LayerNorm
+is `norm="torch"` (`nn.LayerNorm`, the default) or `norm="hip"`
+(`HipLayerNorm`: the fused row kernels, with the residual add in front of
+`ln_2` folded into it). Attention is `attention="torch"`
 (`nn.MultiheadAttention`, the default) or `attention="hip"`
 (`HipSelfAttention`: the fused short-sequence kernels, at most 64 tokens,
-heads of 16, 32 or 64). Both have the same parameters under the same names.
+heads of 16, 32 or 64). The two switches are independent, and every
+combination has the same parameters under the same names.
 """
 
 from __future__ import annotations
@@ -23,24 +26,33 @@ import torch
 from torch import nn
 
 from .attention import HipSelfAttention
+from .layernorm import HipLayerNorm
 from .toy import HipLinear
+
+
+def _layer_norm(norm: str, hidden: int) -> nn.Module:
+    if norm not in ("torch", "hip"):
+        raise ValueError(f"norm must be 'torch' or 'hip', got {norm!r}")
+    cls = HipLayerNorm if norm == "hip" else nn.LayerNorm
+    return cls(hidden, eps=1e-6)
 
 
 class EncoderBlock(nn.Module):
     def __init__(self, hidden: int, heads: int, mlp: int,
-                 attention: str = "torch"):
+                 attention: str = "torch", norm: str = "torch"):
         super().__init__()
         if attention not in ("torch", "hip"):
             raise ValueError(f"attention must be 'torch' or 'hip', "
                              f"got {attention!r}")
         self.hip_attention = attention == "hip"
-        self.ln_1 = nn.LayerNorm(hidden, eps=1e-6)
+        self.hip_norm = norm == "hip"
+        self.ln_1 = _layer_norm(norm, hidden)
         if self.hip_attention:
             self.self_attention = HipSelfAttention(hidden, heads)
         else:
             self.self_attention = nn.MultiheadAttention(hidden, heads,
                                                         batch_first=True)
-        self.ln_2 = nn.LayerNorm(hidden, eps=1e-6)
+        self.ln_2 = _layer_norm(norm, hidden)
         self.mlp = nn.Sequential(
             nn.Linear(hidden, mlp), nn.GELU(), nn.Linear(mlp, hidden))
 
@@ -50,6 +62,9 @@ class EncoderBlock(nn.Module):
             y = self.self_attention(y)
         else:
             y, _ = self.self_attention(y, y, y, need_weights=False)
+        if self.hip_norm:  # x + y and ln_2 of it in one pass
+            x, y = self.ln_2(y, residual=x)
+            return x + self.mlp(y)
         x = x + y
         return x + self.mlp(self.ln_2(x))
 
@@ -58,7 +73,7 @@ class VisionTransformer(nn.Module):
     def __init__(self, image_size: int = 224, patch: int = 32,
                  layers: int = 24, hidden: int = 1024, heads: int = 16,
                  mlp: int = 4096, num_classes: int = 1000,
-                 attention: str = "torch"):
+                 attention: str = "torch", norm: str = "torch"):
         super().__init__()
         self.patch = patch
         self.conv_proj = nn.Conv2d(3, hidden, kernel_size=patch, stride=patch)
@@ -67,9 +82,9 @@ class VisionTransformer(nn.Module):
         self.pos_embedding = nn.Parameter(
             torch.empty(1, n_tokens, hidden).normal_(std=0.02))
         self.encoder = nn.ModuleList(
-            EncoderBlock(hidden, heads, mlp, attention)
+            EncoderBlock(hidden, heads, mlp, attention, norm)
             for _ in range(layers))
-        self.ln = nn.LayerNorm(hidden, eps=1e-6)
+        self.ln = _layer_norm(norm, hidden)
         self.head = HipLinear(hidden, num_classes)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -82,14 +97,15 @@ class VisionTransformer(nn.Module):
         return self.head(self.ln(x[:, 0]))
 
 
-def vit_l_32(num_classes: int = 1000,
-             attention: str = "torch") -> VisionTransformer:
-    return VisionTransformer(num_classes=num_classes, attention=attention)
+def vit_l_32(num_classes: int = 1000, attention: str = "torch",
+             norm: str = "torch") -> VisionTransformer:
+    return VisionTransformer(num_classes=num_classes, attention=attention,
+                             norm=norm)
 
 
-def vit_tiny(num_classes: int = 10,
-             attention: str = "torch") -> VisionTransformer:
+def vit_tiny(num_classes: int = 10, attention: str = "torch",
+             norm: str = "torch") -> VisionTransformer:
     """Small configuration for tests."""
     return VisionTransformer(image_size=64, patch=16, layers=2, hidden=64,
                              heads=4, mlp=128, num_classes=num_classes,
-                             attention=attention)
+                             attention=attention, norm=norm)

@@ -120,6 +120,46 @@ def self_attention(qkv: torch.Tensor, heads: int) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------
+# Fused LayerNorm, with or without the residual add (csrc/layernorm_kernels.hip)
+# ---------------------------------------------------------------------------
+def _ln_operands(*tensors):
+    """Contiguous device operands; float32 under autocast (torch's own policy
+    for layer_norm, as `cross_entropy` does for the losses)."""
+    if torch.is_autocast_enabled("cuda"):
+        tensors = tuple(t.float() for t in tensors)
+    return (tensors[0].contiguous(),) + tuple(tensors[1:])
+
+
+def layer_norm(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
+               eps: float = 1e-5) -> torch.Tensor:
+    """F.layer_norm over the last dimension. On the GPU one wave normalises
+    one row out of registers, forward and backward (last dimension a multiple
+    of 4 up to 2048, fp32 or bf16 storage alike for all operands, fp32
+    arithmetic; other shapes raise). The weight and bias gradients are summed
+    in a fixed order without atomics: run to run the same bits."""
+    if x.is_cuda:
+        x, weight, bias = _ln_operands(x, weight, bias)
+        return ext().layer_norm_autograd(x, weight, bias, eps)
+    return F.layer_norm(x, x.shape[-1:], weight, bias, eps)
+
+
+def add_layer_norm(x: torch.Tensor, residual: torch.Tensor,
+                   weight: torch.Tensor, bias: torch.Tensor,
+                   eps: float = 1e-5):
+    """(s, y) with s = x + residual and y = layer_norm(s): the residual add
+    folded into the LayerNorm that follows it, one pass over the rows forward
+    and one backward. `s` is rounded to the storage dtype and `y` is computed
+    from that rounded `s`. Shapes and dtypes as `layer_norm`."""
+    if x.is_cuda:
+        x, residual, weight, bias = _ln_operands(x, residual, weight, bias)
+        s, y = ext().add_layer_norm_autograd(x, residual.contiguous(), weight,
+                                             bias, eps)
+        return s, y
+    s = x + residual
+    return s, F.layer_norm(s, s.shape[-1:], weight, bias, eps)
+
+
+# ---------------------------------------------------------------------------
 # Losses (reference: CE at single_gpu.py:24, MSE at multinode_torchrun.py:46;
 # both take float probability/value targets of the same shape as the output)
 # ---------------------------------------------------------------------------

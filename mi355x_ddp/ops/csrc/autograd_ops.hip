@@ -134,7 +134,64 @@ struct AttnFn : public torch::autograd::Function<AttnFn> {
   }
 };
 
+// Fused LayerNorm. Saved for the backward: the input, the forward's row
+// statistics and the weight; the output is not kept.
+struct LayerNormFn : public torch::autograd::Function<LayerNormFn> {
+  static torch::Tensor forward(AutogradContext* ctx, torch::Tensor x,
+                               torch::Tensor w, torch::Tensor b, double eps) {
+    auto outs = ln_fwd(x, w, b, eps);  // (y, row_stats)
+    ctx->save_for_backward({x, outs[1], w});
+    return outs[0];
+  }
+
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    auto saved = ctx->get_saved_variables();
+    auto g = ln_bwd(grads[0].contiguous(), saved[0], saved[1], saved[2]);
+    return {g[0], g[1], g[2], torch::Tensor()};
+  }
+};
+
+// s = x + residual, y = LayerNorm(s), both returned. The backward re-reads s
+// (saved with the statistics and the weight) and folds the gradient arriving
+// at s into dx; ONE dx tensor is the gradient of x and of the residual.
+struct AddLayerNormFn : public torch::autograd::Function<AddLayerNormFn> {
+  static variable_list forward(AutogradContext* ctx, torch::Tensor x,
+                               torch::Tensor r, torch::Tensor w,
+                               torch::Tensor b, double eps) {
+    auto outs = ln_fwd(x, w, b, eps, r);  // (s, y, row_stats)
+    ctx->save_for_backward({outs[0], outs[2], w});
+    ctx->set_materialize_grads(false);
+    return {outs[0], outs[1]};
+  }
+
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    const auto& ds = grads[0];
+    const auto& dy = grads[1];
+    if (!dy.defined())  // only s was used: the add's own backward
+      return {ds, ds, torch::Tensor(), torch::Tensor(), torch::Tensor()};
+    auto saved = ctx->get_saved_variables();
+    auto g = ln_bwd(dy.contiguous(), saved[0], saved[1], saved[2],
+                    ds.defined()
+                        ? c10::optional<torch::Tensor>(ds.contiguous())
+                        : c10::nullopt);
+    return {g[0], g[0], g[1], g[2], torch::Tensor()};
+  }
+};
+
 }  // namespace
+
+torch::Tensor layer_norm_autograd(torch::Tensor x, torch::Tensor weight,
+                                  torch::Tensor bias, double eps) {
+  return LayerNormFn::apply(x, weight, bias, eps);
+}
+
+std::vector<torch::Tensor> add_layer_norm_autograd(torch::Tensor x,
+                                                   torch::Tensor residual,
+                                                   torch::Tensor weight,
+                                                   torch::Tensor bias,
+                                                   double eps) {
+  return AddLayerNormFn::apply(x, residual, weight, bias, eps);
+}
 
 torch::Tensor linear_autograd(torch::Tensor x, torch::Tensor w,
                               c10::optional<torch::Tensor> b) {

@@ -19,6 +19,13 @@ torch::Tensor linear_autograd(torch::Tensor x, torch::Tensor w,
 torch::Tensor mse_autograd(torch::Tensor y, torch::Tensor t);
 torch::Tensor ce_autograd(torch::Tensor y, torch::Tensor t);
 torch::Tensor attention_autograd(torch::Tensor qkv, int64_t heads);
+torch::Tensor layer_norm_autograd(torch::Tensor x, torch::Tensor weight,
+                                  torch::Tensor bias, double eps);
+std::vector<torch::Tensor> add_layer_norm_autograd(torch::Tensor x,
+                                                   torch::Tensor residual,
+                                                   torch::Tensor weight,
+                                                   torch::Tensor bias,
+                                                   double eps);
 
 // The run tracker behind PersistentToyStep: shard_run.h's OrderedRuns over
 // the pointer-level launchers, toy_multistep_launch at world 1 and
@@ -277,6 +284,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_bwd", &mi355x::attn_bwd, py::arg("dout"), py::arg("qkv"),
         py::arg("row_stats"), py::arg("heads"),
         py::arg("dqkv") = c10::nullopt);
+  m.def("ln_fwd", &mi355x::ln_fwd, py::arg("x"), py::arg("weight"),
+        py::arg("bias"), py::arg("eps"), py::arg("residual") = c10::nullopt,
+        py::arg("y") = c10::nullopt, py::arg("row_stats") = c10::nullopt,
+        py::arg("s") = c10::nullopt);
+  m.def("ln_bwd", &mi355x::ln_bwd, py::arg("dy"), py::arg("ln_input"),
+        py::arg("row_stats"), py::arg("weight"), py::arg("ds") = c10::nullopt,
+        py::arg("dx") = c10::nullopt, py::arg("dgamma") = c10::nullopt,
+        py::arg("dbeta") = c10::nullopt);
+  m.def("ln_grid_cap", &mi355x::ln_grid_cap);
   m.def("gemm_bf16", &mi355x::gemm_bf16, py::arg("x"), py::arg("w"),
         py::arg("bias") = c10::nullopt);
   m.def("ce_fwd", &mi355x::ce_fwd);
@@ -411,6 +427,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ce_autograd", &mi355x::ce_autograd);
   m.def("attention_autograd", &mi355x::attention_autograd, py::arg("qkv"),
         py::arg("heads"));
+  m.def("layer_norm_autograd", &mi355x::layer_norm_autograd, py::arg("x"),
+        py::arg("weight"), py::arg("bias"), py::arg("eps"));
+  m.def("add_layer_norm_autograd", &mi355x::add_layer_norm_autograd,
+        py::arg("x"), py::arg("residual"), py::arg("weight"), py::arg("bias"),
+        py::arg("eps"));
 
   py::class_<mi355x::ReducerCore, std::shared_ptr<mi355x::ReducerCore>>(
       m, "ReducerCore")

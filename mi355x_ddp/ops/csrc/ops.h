@@ -2,7 +2,8 @@
 // Implementations in kernels.hip, for the toy training-step family
 // (toy_fused_fwd_bwd, toy_multistep*) toy_kernels.hip, and for the
 // flat-bucket optimizers optim_kernels.hip, for the fused self-attention
-// attention_kernels.hip; bound to Python in bindings.hip.
+// attention_kernels.hip, for the fused LayerNorm layernorm_kernels.hip; bound
+// to Python in bindings.hip.
 #pragma once
 #include <torch/extension.h>
 #include <cstdint>
@@ -51,6 +52,33 @@ std::vector<torch::Tensor> attn_fwd(
 torch::Tensor attn_bwd(torch::Tensor dout, torch::Tensor qkv,
                        torch::Tensor row_stats, int64_t heads,
                        c10::optional<torch::Tensor> dqkv = c10::nullopt);
+
+// Fused LayerNorm over the last dimension, optionally with the residual add
+// in front of it (layernorm_kernels.hip). Rows are the flattened leading
+// dimensions of a contiguous x; E = x.size(-1), E % 4 == 0, 4 <= E <= 2048;
+// every operand f32 or bf16 alike, arithmetic and row_stats in f32. Anything
+// else is refused before a launch, and no rows launches nothing.
+// ln_fwd returns (y, row_stats f32 [R, 2] = (mean, rstd)) or, with a
+// residual, (s, y, row_stats): s = x + residual rounded to the storage dtype,
+// y = LN(s) of that rounded s.
+// ln_bwd takes the LN input (x, or s) and returns (dx, dgamma, dbeta); `ds`,
+// the gradient arriving at s, is added into dx. dgamma/dbeta are reduced
+// without atomics in an order fixed by the shape, so they are reproducible.
+// Results may be preallocated (contiguous, 16-byte aligned).
+// ln_grid_cap: the compile-time cap on the row kernels' grid.
+std::vector<torch::Tensor> ln_fwd(
+    torch::Tensor x, torch::Tensor weight, torch::Tensor bias, double eps,
+    c10::optional<torch::Tensor> residual = c10::nullopt,
+    c10::optional<torch::Tensor> y = c10::nullopt,
+    c10::optional<torch::Tensor> row_stats = c10::nullopt,
+    c10::optional<torch::Tensor> s = c10::nullopt);
+std::vector<torch::Tensor> ln_bwd(
+    torch::Tensor dy, torch::Tensor ln_input, torch::Tensor row_stats,
+    torch::Tensor weight, c10::optional<torch::Tensor> ds = c10::nullopt,
+    c10::optional<torch::Tensor> dx = c10::nullopt,
+    c10::optional<torch::Tensor> dgamma = c10::nullopt,
+    c10::optional<torch::Tensor> dbeta = c10::nullopt);
+int64_t ln_grid_cap();
 
 // Cross-entropy with class-probability targets (C may be 1: the reference's
 // degenerate Linear(20,1) case, single_gpu.py:24 + utils.py:7).

@@ -46,9 +46,11 @@ def load_train_objs(dataset_size: int = 2048):
         from mi355x_ddp.models import vit_l_32
         # the reference imports it but leaves it commented out (ref
         # multigpu_profile.py:24); here it runs. MI355X_VIT_ATTENTION=hip
-        # takes the fused short-sequence attention kernels
+        # takes the fused short-sequence attention kernels,
+        # MI355X_VIT_NORM=hip the fused LayerNorm kernels
         model = vit_l_32(
-            attention=os.environ.get("MI355X_VIT_ATTENTION", "torch"))
+            attention=os.environ.get("MI355X_VIT_ATTENTION", "torch"),
+            norm=os.environ.get("MI355X_VIT_NORM", "torch"))
     else:
         model = resnet50()
     train_set = RandomImageDataset(dataset_size, shape)

@@ -1,7 +1,8 @@
 """Time ViT-L/32 training steps through the native engine (multi-bucket
 reducer + fused SGD; the model the reference imports but leaves commented
 out — multigpu_profile.py:24). MI355X_AUTOCAST_BF16=1 for bf16,
-MI355X_VIT_ATTENTION=hip for the fused short-sequence attention kernels."""
+MI355X_VIT_ATTENTION=hip for the fused short-sequence attention kernels,
+MI355X_VIT_NORM=hip for the fused LayerNorm kernels."""
 import os
 import sys
 import time
@@ -19,7 +20,8 @@ bf16 = os.environ.get("MI355X_AUTOCAST_BF16") == "1"
 torch.manual_seed(0)
 dev = "cuda:0"
 attention = os.environ.get("MI355X_VIT_ATTENTION", "torch")
-model = vit_l_32(attention=attention).to(dev)
+norm = os.environ.get("MI355X_VIT_NORM", "torch")
+model = vit_l_32(attention=attention, norm=norm).to(dev)
 x = torch.rand(32, 3, 224, 224, device=dev)
 t = torch.rand(32, 1000, device=dev)
 params = list(model.parameters())
