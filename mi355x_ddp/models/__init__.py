@@ -3,3 +3,4 @@ from .resnet import resnet50, ResNet  # noqa: F401
 from .vit import vit_l_32, vit_tiny, VisionTransformer  # noqa: F401
 from .attention import HipSelfAttention  # noqa: F401
 from .layernorm import HipLayerNorm  # noqa: F401
+from .mlp import HipMlp  # noqa: F401

@@ -9,15 +9,20 @@ hidden 1024, MLP 4096, 16 heads, learned position embeddings, pre-norm
 encoder blocks, class token head) so the parameter census and DDP
 gradient payload (~305 M params, ~1.2 GB fp32 grads) are the real thing.
 
-GELU runs through PyTorch-ROCm (the same scoping as ResNet's convs, SURVEY
-§2.2 N11); the classifier head uses the hand-written MFMA linear. LayerNorm
+The classifier head uses the hand-written MFMA linear. The encoder MLP is
+`mlp="torch"` (`nn.Sequential(Linear, GELU, Linear)` through PyTorch-ROCm,
+the default) or `mlp="hip"` (`HipMlp`: the tiled MFMA GEMMs with the bias
+adds, GELU, GELU' and the bias gradients in their epilogues). LayerNorm
 is `norm="torch"` (`nn.LayerNorm`, the default) or `norm="hip"`
 (`HipLayerNorm`: the fused row kernels, with the residual add in front of
 `ln_2` folded into it). Attention is `attention="torch"`
 (`nn.MultiheadAttention`, the default) or `attention="hip"`
 (`HipSelfAttention`: the fused short-sequence kernels, at most 64 tokens,
-heads of 16, 32 or 64). The two switches are independent, and every
-combination has the same parameters under the same names.
+heads of 16, 32 or 64). The three switches are independent, and every
+combination has the same parameters under the same names. In
+`VisionTransformer` and `EncoderBlock`, where `mlp` already is the MLP's
+width, the switch is spelled `mlp_impl`; `vit_l_32` and `vit_tiny` take it as
+`mlp`.
 """
 
 from __future__ import annotations
@@ -27,6 +32,7 @@ from torch import nn
 
 from .attention import HipSelfAttention
 from .layernorm import HipLayerNorm
+from .mlp import HipMlp
 from .toy import HipLinear
 
 
@@ -39,11 +45,15 @@ def _layer_norm(norm: str, hidden: int) -> nn.Module:
 
 class EncoderBlock(nn.Module):
     def __init__(self, hidden: int, heads: int, mlp: int,
-                 attention: str = "torch", norm: str = "torch"):
+                 attention: str = "torch", norm: str = "torch",
+                 mlp_impl: str = "torch"):
         super().__init__()
         if attention not in ("torch", "hip"):
             raise ValueError(f"attention must be 'torch' or 'hip', "
                              f"got {attention!r}")
+        if mlp_impl not in ("torch", "hip"):
+            raise ValueError(f"mlp_impl (mlp= of vit_l_32 / vit_tiny) must be "
+                             f"'torch' or 'hip', got {mlp_impl!r}")
         self.hip_attention = attention == "hip"
         self.hip_norm = norm == "hip"
         self.ln_1 = _layer_norm(norm, hidden)
@@ -53,8 +63,11 @@ class EncoderBlock(nn.Module):
             self.self_attention = nn.MultiheadAttention(hidden, heads,
                                                         batch_first=True)
         self.ln_2 = _layer_norm(norm, hidden)
-        self.mlp = nn.Sequential(
-            nn.Linear(hidden, mlp), nn.GELU(), nn.Linear(mlp, hidden))
+        if mlp_impl == "hip":
+            self.mlp = HipMlp(hidden, mlp)
+        else:
+            self.mlp = nn.Sequential(
+                nn.Linear(hidden, mlp), nn.GELU(), nn.Linear(mlp, hidden))
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         y = self.ln_1(x)
@@ -73,7 +86,8 @@ class VisionTransformer(nn.Module):
     def __init__(self, image_size: int = 224, patch: int = 32,
                  layers: int = 24, hidden: int = 1024, heads: int = 16,
                  mlp: int = 4096, num_classes: int = 1000,
-                 attention: str = "torch", norm: str = "torch"):
+                 attention: str = "torch", norm: str = "torch",
+                 mlp_impl: str = "torch"):
         super().__init__()
         self.patch = patch
         self.conv_proj = nn.Conv2d(3, hidden, kernel_size=patch, stride=patch)
@@ -82,7 +96,7 @@ class VisionTransformer(nn.Module):
         self.pos_embedding = nn.Parameter(
             torch.empty(1, n_tokens, hidden).normal_(std=0.02))
         self.encoder = nn.ModuleList(
-            EncoderBlock(hidden, heads, mlp, attention, norm)
+            EncoderBlock(hidden, heads, mlp, attention, norm, mlp_impl)
             for _ in range(layers))
         self.ln = _layer_norm(norm, hidden)
         self.head = HipLinear(hidden, num_classes)
@@ -98,14 +112,14 @@ class VisionTransformer(nn.Module):
 
 
 def vit_l_32(num_classes: int = 1000, attention: str = "torch",
-             norm: str = "torch") -> VisionTransformer:
+             norm: str = "torch", mlp: str = "torch") -> VisionTransformer:
     return VisionTransformer(num_classes=num_classes, attention=attention,
-                             norm=norm)
+                             norm=norm, mlp_impl=mlp)
 
 
 def vit_tiny(num_classes: int = 10, attention: str = "torch",
-             norm: str = "torch") -> VisionTransformer:
+             norm: str = "torch", mlp: str = "torch") -> VisionTransformer:
     """Small configuration for tests."""
     return VisionTransformer(image_size=64, patch=16, layers=2, hidden=64,
                              heads=4, mlp=128, num_classes=num_classes,
-                             attention=attention, norm=norm)
+                             attention=attention, norm=norm, mlp_impl=mlp)

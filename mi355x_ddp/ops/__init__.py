@@ -2,7 +2,7 @@
 
 Every op has two paths:
 - device tensors -> the hand-written CDNA4 HIP kernels in `mi355x_ddp._C`
-  (MFMA-tiled linear, CE/MSE, fused SGD / momentum SGD / AdamW, global
+  (MFMA-tiled linear, the tiled-GEMM MLP, CE/MSE, fused SGD / momentum SGD / AdamW, global
   grad-norm clipping, bucket copies). If the extension
   is missing on a GPU host this layer raises — there is NO silent eager
   fallback on the GPU.
@@ -89,6 +89,50 @@ def linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None):
             return y.reshape(*lead, w.shape[0])
         return ext().linear_autograd(x, w, b)
     return F.linear(x, w, b)
+
+
+# ---------------------------------------------------------------------------
+# Linear -> GELU (-> Linear) on the tiled GEMMs (csrc/gemm_kernels.hip)
+# ---------------------------------------------------------------------------
+def _gemm_operands(x, *params):
+    """x flattened to rows, everything contiguous (a no-op for parameters as
+    nn.Linear holds them) and in the autocast dtype under autocast
+    (nn.Linear's policy, as `linear` does)."""
+    if torch.is_autocast_enabled("cuda"):
+        dt = torch.get_autocast_dtype("cuda")
+        x, params = x.to(dt), tuple(p.to(dt) for p in params)
+    return (x.reshape(-1, x.shape[-1]).contiguous(),) \
+        + tuple(p.contiguous() for p in params)
+
+
+def mlp(x: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor,
+        w2: torch.Tensor, b2: torch.Tensor) -> torch.Tensor:
+    """linear(gelu(linear(x, w1, b1)), w2, b2) with exact (erf) GELU: the
+    transformer MLP. On the GPU it is six launches of one LDS-tiled MFMA GEMM
+    kernel, two forward and four backward; both bias adds, GELU, the
+    multiplication by GELU' and both bias gradients ride in the GEMMs'
+    epilogues, so no elementwise kernel runs. Every feature dimension must be
+    a multiple of 16, the dtype fp32 or bf16 (other inputs raise); leading
+    dimensions are flattened and restored. GELU is applied to the linear
+    output as stored (rounded to bf16 under bf16), as torch does; weight and
+    bias gradients are the same bits run to run. The CPU path is the formula
+    in plain torch ops."""
+    if x.is_cuda:
+        lead = x.shape[:-1]
+        y = ext().mlp_autograd(*_gemm_operands(x, w1, b1, w2, b2))
+        return y.reshape(*lead, w2.shape[0])
+    return F.linear(F.gelu(F.linear(x, w1, b1)), w2, b2)
+
+
+def linear_gelu(x: torch.Tensor, w: torch.Tensor,
+                b: torch.Tensor) -> torch.Tensor:
+    """gelu(linear(x, w, b)), the first half of `mlp` on its own: the bias add
+    and GELU in the forward GEMM's epilogue. Shapes and dtypes as `mlp`."""
+    if x.is_cuda:
+        lead = x.shape[:-1]
+        y = ext().linear_gelu_autograd(*_gemm_operands(x, w, b))
+        return y.reshape(*lead, w.shape[0])
+    return F.gelu(F.linear(x, w, b))
 
 
 # ---------------------------------------------------------------------------

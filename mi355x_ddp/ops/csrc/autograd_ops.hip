@@ -178,7 +178,81 @@ struct AddLayerNormFn : public torch::autograd::Function<AddLayerNormFn> {
   }
 };
 
+// The two GEMMs that turn the gradient arriving at h into the gradients of a
+// linear layer's input, weight and bias; what is not needed is not computed.
+variable_list linear_grads(AutogradContext* ctx, const torch::Tensor& dh,
+                           const torch::Tensor& x, const torch::Tensor& w,
+                           int first) {
+  torch::Tensor dx, dw, db;
+  if (ctx->needs_input_grad(first + 1) || ctx->needs_input_grad(first + 2)) {
+    auto g = gemm_tn(dh, x);
+    dw = g[0], db = g[1];
+  }
+  if (ctx->needs_input_grad(first)) dx = gemm_nn(dh, w);
+  return {dx, dw, db};
+}
+
+// gelu(x w^T + b) on the tiled GEMMs: the bias add and GELU ride in the
+// forward GEMM's epilogue. The backward has no second weight to fold gelu'
+// into, so dh = da * gelu'(h) is one elementwise HIP kernel (gelu_grad_mul)
+// ahead of TN and NN. Saved: x, w and h, the linear output.
+struct LinearGeluFn : public torch::autograd::Function<LinearGeluFn> {
+  static torch::Tensor forward(AutogradContext* ctx, torch::Tensor x,
+                               torch::Tensor w, torch::Tensor b) {
+    auto outs = gemm_nt(x, w, b, /*gelu=*/true);  // (h, a)
+    ctx->save_for_backward({x, w, outs[0]});
+    return outs[1];
+  }
+
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    auto saved = ctx->get_saved_variables();
+    const auto &x = saved[0], &w = saved[1], &h = saved[2];
+    auto dh = gelu_grad_mul(grads[0].contiguous(), h);
+    return linear_grads(ctx, dh, x, w, 0);
+  }
+};
+
+// Linear -> GELU -> Linear. Forward: NT+GELU, NT+bias. Backward: TN(dy, a),
+// NN+GELU'(dy, w2, h), TN(dh, x), NN(dh, w1): six GEMM launches and no
+// elementwise kernel. Saved: x, h, a and the weights.
+struct MlpFn : public torch::autograd::Function<MlpFn> {
+  static torch::Tensor forward(AutogradContext* ctx, torch::Tensor x,
+                               torch::Tensor w1, torch::Tensor b1,
+                               torch::Tensor w2, torch::Tensor b2) {
+    auto ha = gemm_nt(x, w1, b1, /*gelu=*/true);  // (h, a)
+    ctx->save_for_backward({x, ha[0], ha[1], w1, w2});
+    return gemm_nt(ha[1], w2, b2)[0];
+  }
+
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    auto saved = ctx->get_saved_variables();
+    const auto &x = saved[0], &h = saved[1], &a = saved[2], &w1 = saved[3],
+               &w2 = saved[4];
+    auto dy = grads[0].contiguous();
+    torch::Tensor dw2, db2;
+    if (ctx->needs_input_grad(3) || ctx->needs_input_grad(4)) {
+      auto g = gemm_tn(dy, a);
+      dw2 = g[0], db2 = g[1];
+    }
+    variable_list first = {torch::Tensor(), torch::Tensor(), torch::Tensor()};
+    if (ctx->needs_input_grad(0) || ctx->needs_input_grad(1) ||
+        ctx->needs_input_grad(2))
+      first = linear_grads(ctx, gemm_nn(dy, w2, h), x, w1, 0);
+    return {first[0], first[1], first[2], dw2, db2};
+  }
+};
+
 }  // namespace
+
+torch::Tensor mlp_autograd(torch::Tensor x, torch::Tensor w1, torch::Tensor b1,
+                           torch::Tensor w2, torch::Tensor b2) {
+  return MlpFn::apply(x, w1, b1, w2, b2);
+}
+
+torch::Tensor linear_gelu_autograd(torch::Tensor x, torch::Tensor w,
+                                   torch::Tensor b) {
+  return LinearGeluFn::apply(x, w, b);
+}
 
 torch::Tensor layer_norm_autograd(torch::Tensor x, torch::Tensor weight,
                                   torch::Tensor bias, double eps) {

@@ -26,6 +26,10 @@ std::vector<torch::Tensor> add_layer_norm_autograd(torch::Tensor x,
                                                    torch::Tensor weight,
                                                    torch::Tensor bias,
                                                    double eps);
+torch::Tensor mlp_autograd(torch::Tensor x, torch::Tensor w1, torch::Tensor b1,
+                           torch::Tensor w2, torch::Tensor b2);
+torch::Tensor linear_gelu_autograd(torch::Tensor x, torch::Tensor w,
+                                   torch::Tensor b);
 
 // The run tracker behind PersistentToyStep: shard_run.h's OrderedRuns over
 // the pointer-level launchers, toy_multistep_launch at world 1 and
@@ -293,6 +297,33 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dx") = c10::nullopt, py::arg("dgamma") = c10::nullopt,
         py::arg("dbeta") = c10::nullopt);
   m.def("ln_grid_cap", &mi355x::ln_grid_cap);
+  m.def(
+      "gemm_nt",
+      [](torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> bias,
+         bool gelu, c10::optional<torch::Tensor> y,
+         c10::optional<torch::Tensor> h) -> py::object {
+        auto outs = mi355x::gemm_nt(x, w, bias, gelu, y, h);
+        if (gelu) return py::make_tuple(outs[0], outs[1]);  // (h, a)
+        return py::cast(outs[0]);
+      },
+      py::arg("x"), py::arg("w"), py::arg("bias") = c10::nullopt,
+      py::arg("gelu") = false, py::arg("y") = c10::nullopt,
+      py::arg("h") = c10::nullopt);
+  m.def("gemm_nn", &mi355x::gemm_nn, py::arg("dy"), py::arg("w"),
+        py::arg("gelu_grad_of") = c10::nullopt, py::arg("dx") = c10::nullopt);
+  m.def(
+      "gemm_tn",
+      [](torch::Tensor dy, torch::Tensor x, c10::optional<torch::Tensor> dw,
+         c10::optional<torch::Tensor> db) {
+        auto outs = mi355x::gemm_tn(dy, x, dw, db);
+        return py::make_tuple(outs[0], outs[1]);
+      },
+      py::arg("dy"), py::arg("x"), py::arg("dw") = c10::nullopt,
+      py::arg("db") = c10::nullopt);
+  m.def("gemm_tile_shape", []() {
+    const auto t = mi355x::gemm_tile_shape();
+    return py::make_tuple(t[0], t[1], t[2]);
+  });
   m.def("gemm_bf16", &mi355x::gemm_bf16, py::arg("x"), py::arg("w"),
         py::arg("bias") = c10::nullopt);
   m.def("ce_fwd", &mi355x::ce_fwd);
@@ -432,6 +463,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("add_layer_norm_autograd", &mi355x::add_layer_norm_autograd,
         py::arg("x"), py::arg("residual"), py::arg("weight"), py::arg("bias"),
         py::arg("eps"));
+  m.def("mlp_autograd", &mi355x::mlp_autograd, py::arg("x"), py::arg("w1"),
+        py::arg("b1"), py::arg("w2"), py::arg("b2"));
+  m.def("linear_gelu_autograd", &mi355x::linear_gelu_autograd, py::arg("x"),
+        py::arg("w"), py::arg("b"));
 
   py::class_<mi355x::ReducerCore, std::shared_ptr<mi355x::ReducerCore>>(
       m, "ReducerCore")

@@ -2,8 +2,8 @@
 // Implementations in kernels.hip, for the toy training-step family
 // (toy_fused_fwd_bwd, toy_multistep*) toy_kernels.hip, and for the
 // flat-bucket optimizers optim_kernels.hip, for the fused self-attention
-// attention_kernels.hip, for the fused LayerNorm layernorm_kernels.hip; bound
-// to Python in bindings.hip.
+// attention_kernels.hip, for the fused LayerNorm layernorm_kernels.hip, for
+// the tiled GEMMs gemm_kernels.hip; bound to Python in bindings.hip.
 #pragma once
 #include <torch/extension.h>
 #include <cstdint>
@@ -79,6 +79,37 @@ std::vector<torch::Tensor> ln_bwd(
     c10::optional<torch::Tensor> dgamma = c10::nullopt,
     c10::optional<torch::Tensor> dbeta = c10::nullopt);
 int64_t ln_grid_cap();
+
+// LDS-tiled MFMA GEMMs for transformer-sized linears with the MLP's
+// elementwise work in their epilogues (gemm_kernels.hip). Operands are 2-D,
+// contiguous, 16-byte aligned, f32 or bf16 alike; every feature dimension is
+// a multiple of 16, the row count M is any number >= 0. Anything else is
+// refused before a launch; empty problems launch nothing, and an empty
+// contraction gives zeros (plus the bias). Results may be preallocated.
+// gemm_nt: y[M,N] = x[M,K] w[N,K]^T + bias. With gelu it returns (h, a):
+//   h the linear output rounded to the storage dtype, a = gelu(h) (exact erf
+//   form) of that rounded h; `y` is then the buffer for a.
+// gemm_nn: dx[M,K] = dy[M,N] w[N,K]; with gelu_grad_of = h [M,K] the result
+//   is multiplied by gelu'(h) on its way out.
+// gemm_tn: (dw[N,K] = dy[M,N]^T x[M,K], db[N] = sum_m dy), both overwritten,
+//   summed in an order fixed by the shape: reproducible, no atomics.
+// gemm_tile_shape: (BM, BN, BK) of the workgroup tile.
+// gelu_grad_mul: da * gelu'(h) elementwise, for a GELU whose gradient has no
+//   GEMM to ride in (da and h as the operands above, of one shape).
+std::vector<torch::Tensor> gemm_nt(
+    torch::Tensor x, torch::Tensor w,
+    c10::optional<torch::Tensor> bias = c10::nullopt, bool gelu = false,
+    c10::optional<torch::Tensor> y = c10::nullopt,
+    c10::optional<torch::Tensor> h = c10::nullopt);
+torch::Tensor gemm_nn(torch::Tensor dy, torch::Tensor w,
+                      c10::optional<torch::Tensor> gelu_grad_of = c10::nullopt,
+                      c10::optional<torch::Tensor> dx = c10::nullopt);
+std::vector<torch::Tensor> gemm_tn(
+    torch::Tensor dy, torch::Tensor x,
+    c10::optional<torch::Tensor> dw = c10::nullopt,
+    c10::optional<torch::Tensor> db = c10::nullopt);
+std::vector<int64_t> gemm_tile_shape();
+torch::Tensor gelu_grad_mul(torch::Tensor da, torch::Tensor h);
 
 // Cross-entropy with class-probability targets (C may be 1: the reference's
 // degenerate Linear(20,1) case, single_gpu.py:24 + utils.py:7).

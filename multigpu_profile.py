@@ -47,10 +47,12 @@ def load_train_objs(dataset_size: int = 2048):
         # the reference imports it but leaves it commented out (ref
         # multigpu_profile.py:24); here it runs. MI355X_VIT_ATTENTION=hip
         # takes the fused short-sequence attention kernels,
-        # MI355X_VIT_NORM=hip the fused LayerNorm kernels
+        # MI355X_VIT_NORM=hip the fused LayerNorm kernels, MI355X_VIT_MLP=hip
+        # the tiled-GEMM MLP
         model = vit_l_32(
             attention=os.environ.get("MI355X_VIT_ATTENTION", "torch"),
-            norm=os.environ.get("MI355X_VIT_NORM", "torch"))
+            norm=os.environ.get("MI355X_VIT_NORM", "torch"),
+            mlp=os.environ.get("MI355X_VIT_MLP", "torch"))
     else:
         model = resnet50()
     train_set = RandomImageDataset(dataset_size, shape)

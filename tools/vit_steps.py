@@ -2,7 +2,8 @@
 reducer + fused SGD; the model the reference imports but leaves commented
 out — multigpu_profile.py:24). MI355X_AUTOCAST_BF16=1 for bf16,
 MI355X_VIT_ATTENTION=hip for the fused short-sequence attention kernels,
-MI355X_VIT_NORM=hip for the fused LayerNorm kernels."""
+MI355X_VIT_NORM=hip for the fused LayerNorm kernels, MI355X_VIT_MLP=hip for
+the tiled-GEMM MLP."""
 import os
 import sys
 import time
@@ -21,7 +22,8 @@ torch.manual_seed(0)
 dev = "cuda:0"
 attention = os.environ.get("MI355X_VIT_ATTENTION", "torch")
 norm = os.environ.get("MI355X_VIT_NORM", "torch")
-model = vit_l_32(attention=attention, norm=norm).to(dev)
+mlp = os.environ.get("MI355X_VIT_MLP", "torch")
+model = vit_l_32(attention=attention, norm=norm, mlp=mlp).to(dev)
 x = torch.rand(32, 3, 224, 224, device=dev)
 t = torch.rand(32, 1000, device=dev)
 params = list(model.parameters())
