@@ -1,4 +1,5 @@
-"""Self-attention block over the fused short-sequence kernels.
+"""Self-attention block over the fused attention kernels (any N up to 4096:
+one workgroup per head up to 64 tokens, the tiled kernels above).
 
 `HipSelfAttention` is `nn.MultiheadAttention(embed_dim, num_heads,
 batch_first=True)` restricted to what ViT uses (self-attention, no mask, no

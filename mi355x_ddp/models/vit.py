@@ -17,12 +17,12 @@ is `norm="torch"` (`nn.LayerNorm`, the default) or `norm="hip"`
 (`HipLayerNorm`: the fused row kernels, with the residual add in front of
 `ln_2` folded into it). Attention is `attention="torch"`
 (`nn.MultiheadAttention`, the default) or `attention="hip"`
-(`HipSelfAttention`: the fused short-sequence kernels, at most 64 tokens,
+(`HipSelfAttention`: the fused attention kernels, any N up to 4096 tokens,
 heads of 16, 32 or 64). The three switches are independent, and every
 combination has the same parameters under the same names. In
 `VisionTransformer` and `EncoderBlock`, where `mlp` already is the MLP's
-width, the switch is spelled `mlp_impl`; `vit_l_32` and `vit_tiny` take it as
-`mlp`.
+width, the switch is spelled `mlp_impl`; `vit_l_32`, `vit_b_16` and `vit_tiny`
+take it as `mlp`.
 """
 
 from __future__ import annotations
@@ -115,6 +115,14 @@ def vit_l_32(num_classes: int = 1000, attention: str = "torch",
              norm: str = "torch", mlp: str = "torch") -> VisionTransformer:
     return VisionTransformer(num_classes=num_classes, attention=attention,
                              norm=norm, mlp_impl=mlp)
+
+
+def vit_b_16(num_classes: int = 1000, attention: str = "torch",
+             norm: str = "torch", mlp: str = "torch") -> VisionTransformer:
+    """torchvision's `vit_b_16`: 197 tokens at 224 px."""
+    return VisionTransformer(patch=16, layers=12, hidden=768, heads=12,
+                             mlp=3072, num_classes=num_classes,
+                             attention=attention, norm=norm, mlp_impl=mlp)
 
 
 def vit_tiny(num_classes: int = 10, attention: str = "torch",

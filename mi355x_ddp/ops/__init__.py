@@ -136,7 +136,7 @@ def linear_gelu(x: torch.Tensor, w: torch.Tensor,
 
 
 # ---------------------------------------------------------------------------
-# Fused short-sequence self-attention (csrc/attention_kernels.hip)
+# Fused self-attention (csrc/attention_kernels.hip)
 # ---------------------------------------------------------------------------
 def self_attention(qkv: torch.Tensor, heads: int) -> torch.Tensor:
     """softmax(Q K^T / sqrt(D)) V per head, on the packed in-projection
@@ -144,9 +144,11 @@ def self_attention(qkv: torch.Tensor, heads: int) -> torch.Tensor:
     and head h at columns h*D.. of each (E = heads*D); the result is
     [B, N, E], ready for the out-projection. No mask, no dropout.
 
-    On the GPU one workgroup per (batch, head) runs the whole head out of
-    LDS, forward and backward (1 <= N <= 64, D in 16/32/64, fp32 or bf16
-    storage, fp32 arithmetic); other shapes raise. Under autocast the input
+    On the GPU, forward and backward, any N up to 4096 (D in 16/32/64, fp32
+    or bf16 storage, fp32 arithmetic); other shapes raise. Up to 64 tokens
+    one workgroup per (batch, head) runs the whole head out of LDS; above,
+    the tiled kernels walk the keys in blocks of 64 with an online softmax
+    and the backward additionally keeps the output. Under autocast the input
     is cast to the autocast dtype, as `linear` does. The CPU path is the
     formula in plain torch ops, the kernels' mirror."""
     if qkv.is_cuda:

@@ -8,6 +8,9 @@
 //                    reciprocal of the row's sum of exponentials
 //   dqkv [B, N, 3E]  the three gradients in qkv's own layout
 //
+// Two kernel families: the short one described here, and below it the tiled
+// one for up to 4096 tokens (k_attn_tiled_*), which shares its helpers.
+//
 // 1 <= N <= 64, D in {16, 32, 64}; no mask, no dropout. A whole (batch, head)
 // problem is smaller than one flash-attention tile, so ONE workgroup of four
 // waves holds all of it in LDS: no online softmax, no split over keys, no
@@ -60,14 +63,34 @@ namespace {
 constexpr int kAttnMaxN = 64;
 constexpr float kLog2e = 1.4426950408889634f;
 
+// Clang vector types and builtins, not the HIP headers' float4, __shfl_xor
+// and the like: under this file's target attribute those stay as CALLS
+// (docs/KERNELS.md, "No header calls").
+using f32x2 = __attribute__((ext_vector_type(2))) float;
+using u32x2 = __attribute__((ext_vector_type(2))) uint32_t;
+
+__device__ __forceinline__ float as_f32(uint32_t u) {
+  return __builtin_bit_cast(float, u);
+}
 __device__ __forceinline__ void load4(const float* p, float v[4]) {
-  const float4 x = *reinterpret_cast<const float4*>(p);
-  v[0] = x.x, v[1] = x.y, v[2] = x.z, v[3] = x.w;
+  const f32x4 x = *reinterpret_cast<const f32x4*>(p);
+  v[0] = x[0], v[1] = x[1], v[2] = x[2], v[3] = x[3];
 }
 __device__ __forceinline__ void load4(const __hip_bfloat16* p, float v[4]) {
-  const uint2 x = *reinterpret_cast<const uint2*>(p);
-  v[0] = __uint_as_float(x.x << 16), v[1] = __uint_as_float(x.x & 0xffff0000u);
-  v[2] = __uint_as_float(x.y << 16), v[3] = __uint_as_float(x.y & 0xffff0000u);
+  const u32x2 x = *reinterpret_cast<const u32x2*>(p);
+  v[0] = as_f32(x[0] << 16), v[1] = as_f32(x[0] & 0xffff0000u);
+  v[2] = as_f32(x[1] << 16), v[3] = as_f32(x[1] & 0xffff0000u);
+}
+// The value of lane `src` (ds_bpermute).
+__device__ __forceinline__ float from_lane(float v, int src) {
+  return __builtin_bit_cast(
+      float,
+      __builtin_amdgcn_ds_bpermute(src << 2, __builtin_bit_cast(int, v)));
+}
+__device__ __forceinline__ void block_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
 // Stage rows [0, NP) x D of one head slice (row stride ld elements) into an
@@ -142,13 +165,16 @@ __device__ __forceinline__ void store_strip(T* dst, size_t ld,
 
 // Reduce over the 16 lanes that share q (one fragment row's 16 columns).
 __device__ __forceinline__ float row16_max(float v) {
+  const int lane = threadIdx.x & 63;
 #pragma unroll
-  for (int off = 8; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+  for (int off = 8; off > 0; off >>= 1)
+    v = fmaxf(v, from_lane(v, lane ^ off));
   return v;
 }
 __device__ __forceinline__ float row16_sum(float v) {
+  const int lane = threadIdx.x & 63;
 #pragma unroll
-  for (int off = 8; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  for (int off = 8; off > 0; off >>= 1) v += from_lane(v, lane ^ off);
   return v;
 }
 
@@ -334,14 +360,353 @@ __global__ __launch_bounds__(256) void k_attn_bwd(const T* __restrict__ qkv,
   }
 }
 
+// ===========================================================================
+// The tiled family: 64 < N <= 4096 (and any N >= 1), same operands and
+// arithmetic. A workgroup owns 64 rows (16 per wave) whose operands stay in
+// A-operand registers (D/4 words per lane, read from global memory once)
+// and walks the other side in blocks of 64 rows that every wave stages
+// together. The next block's global loads are issued right after the current
+// block's LDS stores, ahead of its MFMAs. A 16 x 64 strip goes from
+// D-fragment to A-operand layout through the wave's own piece of LDS: no
+// other wave touches it, so it takes wave-scope ordering and no barrier.
+//
+//   fwd     rows: queries  walks keys     online softmax, O rescaled in place
+//   bwd_q   rows: queries  walks keys     delta = rowsum(dO * O), dQ
+//   bwd_kv  rows: KEYS     walks queries  dK, dV from the TRANSPOSED strips
+//
+// Every result row is written once by the one wave that owns it: no atomics,
+// nothing pre-zeroed. Rows >= N are zero in every operand, never read from
+// global memory and never stored; keys >= N get -inf (forward) or P = 0
+// (backward), so the last block may hold a single row.
+// ===========================================================================
+constexpr int kAttnTiledMaxN = 4096;
+constexpr int kBlk = 64;   // rows per workgroup and per staged block
+constexpr int kStripP = 68;  // pitch of a wave's strip, read rk only
+
+// One block of 64 rows x D, fetched into registers (rows >= N zero) ...
+template <typename T, int D>
+__device__ __forceinline__ void fetch_block(float regs[D / 16][4],
+                                            const T* src, size_t ld, int row0,
+                                            int N) {
+  constexpr int CH = D / 4;
+#pragma unroll
+  for (int u = 0; u < D / 16; ++u) {
+    const int idx = threadIdx.x + u * 256;
+    const int row = row0 + idx / CH, c = (idx % CH) * 4;
+    regs[u][0] = regs[u][1] = regs[u][2] = regs[u][3] = 0.f;
+    if (row < N) load4(src + (size_t)row * ld + c, regs[u]);
+  }
+}
+// ... and put into its LDS image.
+template <int D>
+__device__ __forceinline__ void put_block(float* img, int pitch,
+                                          const float regs[D / 16][4]) {
+  constexpr int CH = D / 4;
+#pragma unroll
+  for (int u = 0; u < D / 16; ++u) {
+    const int idx = threadIdx.x + u * 256;
+    *reinterpret_cast<f32x4*>(&img[(idx / CH) * pitch + (idx % CH) * 4]) =
+        f32x4{regs[u][0], regs[u][1], regs[u][2], regs[u][3]};
+  }
+}
+
+// The lane's A operand of one row for a contraction over D, from global.
+template <typename T, int D>
+__device__ __forceinline__ void load_a(float a[D / 4], const T* src, size_t ld,
+                                       int row, int N, int q) {
+#pragma unroll
+  for (int s = 0; s < D / 4; ++s)
+    a[s] = row < N ? ldf(&src[(size_t)row * ld + s * 4 + q]) : 0.f;
+}
+
+// Fragment-layout strip -> the wave's own LDS piece. LDS serves one wave's
+// accesses in program order; the fences keep the compiler from reordering
+// the stores and the loads around them.
+__device__ __forceinline__ void strip_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ void put_strip(float* strip, const f32x4 f[4],
+                                          int nt, int r, int q) {
+  strip_sync();  // the previous use's loads come first
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (j < nt) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        strip[(q * 4 + i) * kStripP + j * 16 + r] = f[j][i];
+    }
+  strip_sync();
+}
+
+struct TiledBlock {
+  int b, h, blk;  // batch, head, 64-row block of this workgroup
+};
+__device__ __forceinline__ TiledBlock tiled_block(int H, int nblk) {
+  const int bh = blockIdx.x / nblk;
+  return {bh / H, bh % H, (int)(blockIdx.x % nblk)};
+}
+
+// Forward. Images: K (rk, 68), V (kr, 80), four strips (P).
+template <typename T, int D>
+__global__ __launch_bounds__(256, 2) void k_attn_tiled_fwd(
+    const T* __restrict__ qkv, T* __restrict__ out, f32x2* __restrict__ stats,
+    int N, int H, int nblk, float scale) {
+  constexpr int PK = 68, PV = 80;
+  __shared__ float sK[kBlk * PK];
+  __shared__ float sV[kBlk * PV];
+  __shared__ float sP[kBlk * kStripP];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r = lane & 15, q = lane >> 4;
+  const TiledBlock w = tiled_block(H, nblk);
+  const size_t E = (size_t)H * D;
+  const T* src = qkv + (size_t)w.b * N * 3 * E + (size_t)w.h * D;
+  const int row0 = w.blk * kBlk + wave * 16;
+  const bool active = row0 < N;  // the others only stage
+  float* strip = sP + wave * 16 * kStripP;
+  const float c = scale * kLog2e;
+
+  float a[D / 4];
+  load_a<T, D>(a, src, 3 * E, row0 + r, N, q);
+  float m[4], l[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) m[i] = -INFINITY;
+  f32x4 o[D / 16] = {};
+
+  float kreg[D / 16][4], vreg[D / 16][4];
+  fetch_block<T, D>(kreg, src + E, 3 * E, 0, N);
+  fetch_block<T, D>(vreg, src + 2 * E, 3 * E, 0, N);
+  for (int k0 = 0; k0 < N; k0 += kBlk) {
+    block_sync();  // the previous block's reads are done
+    put_block<D>(sK, PK, kreg);
+    put_block<D>(sV, PV, vreg);
+    block_sync();
+    if (k0 + kBlk < N) {
+      fetch_block<T, D>(kreg, src + E, 3 * E, k0 + kBlk, N);
+      fetch_block<T, D>(vreg, src + 2 * E, 3 * E, k0 + kBlk, N);
+    }
+    if (!active) continue;
+    const int nt = min(4, (N - k0 + 15) >> 4);
+    f32x4 s4[4] = {};
+    strip_rk<D>(s4, a, sK, PK, nt, r, q);
+    // online softmax on the fragments: row = row0 + 4q + i, key k0 + 16j + r
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      float mb = -INFINITY;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (j >= nt || k0 + j * 16 + r >= N) s4[j][i] = -INFINITY;
+        mb = fmaxf(mb, s4[j][i]);
+      }
+      // finite: key k0 exists. From m = -inf the factor is exp2(-inf) = 0.
+      const float mn = fmaxf(m[i], row16_max(mb));
+      const float f = __builtin_amdgcn_exp2f((m[i] - mn) * c);
+      m[i] = mn;
+      float sum = 0.f;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float p = __builtin_amdgcn_exp2f((s4[j][i] - mn) * c);
+        s4[j][i] = p;
+        sum += p;
+      }
+      l[i] = l[i] * f + row16_sum(sum);
+#pragma unroll
+      for (int t = 0; t < D / 16; ++t) o[t][i] *= f;
+    }
+    put_strip(strip, s4, nt, r, q);
+    strip_out<D, false>(o, strip, kStripP, 0, sV, PV, nt * 16, r, q);
+  }
+  if (active) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      l[i] = 1.f / l[i];
+      const int row = row0 + q * 4 + i;
+      if (r == 0 && row < N)
+        stats[((size_t)w.b * H + w.h) * N + row] = f32x2{m[i], l[i]};
+    }
+    store_strip<T, D>(out + (size_t)w.b * N * E + (size_t)w.h * D, E, o, row0,
+                      N, l, r, q);
+  }
+}
+
+// P of one fragment element from the saved statistics, as the forward's.
+__device__ __forceinline__ float p_from_stats(float s, f32x2 st, float c,
+                                              bool live) {
+  return live ? __builtin_amdgcn_exp2f((s - st[0]) * c) * st[1] : 0.f;
+}
+
+// Backward, query side. Images: K (S: rk, dQ: kr; 72), V (dP: rk; 68), four
+// strips (dS). Also leaves delta[b, h, row] for k_attn_tiled_bwd_kv.
+template <typename T, int D>
+__global__ __launch_bounds__(256, 2) void k_attn_tiled_bwd_q(
+    const T* __restrict__ qkv, const T* __restrict__ dout,
+    const T* __restrict__ out, const f32x2* __restrict__ stats,
+    float* __restrict__ delta, T* __restrict__ dqkv, int N, int H, int nblk,
+    float scale) {
+  constexpr int PK = 72, PV = 68;
+  __shared__ float sK[kBlk * PK];
+  __shared__ float sV[kBlk * PV];
+  __shared__ float sS[kBlk * kStripP];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r = lane & 15, q = lane >> 4;
+  const TiledBlock w = tiled_block(H, nblk);
+  const size_t E = (size_t)H * D;
+  const size_t hq = (size_t)w.b * N * 3 * E + (size_t)w.h * D;
+  const size_t ho = (size_t)w.b * N * E + (size_t)w.h * D;
+  const size_t hs = ((size_t)w.b * H + w.h) * N;
+  const int row0 = w.blk * kBlk + wave * 16;
+  const bool active = row0 < N;
+  float* strip = sS + wave * 16 * kStripP;
+  const float c = scale * kLog2e;
+
+  float a_q[D / 4], a_do[D / 4];
+  load_a<T, D>(a_q, qkv + hq, 3 * E, row0 + r, N, q);
+  load_a<T, D>(a_do, dout + ho, E, row0 + r, N, q);
+  // delta = the diagonal of dO O^T, by the MFMA steps that form dP = dO V^T:
+  // O's rows in A-operand registers are also its B operand here. Where a row
+  // has one key (O = V) delta then equals dP bit for bit and dS is exactly 0.
+  f32x2 st[4];
+  float dl[4];
+  {
+    float a_o[D / 4];
+    load_a<T, D>(a_o, out + ho, E, row0 + r, N, q);
+    f32x4 t = {};
+#pragma unroll
+    for (int s = 0; s < D / 4; ++s) t = mfma4(a_do[s], a_o[s], t);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {  // fragment row 4q + i, column r
+      const int row = row0 + q * 4 + i;
+      dl[i] = from_lane(t[i], q * 16 + q * 4 + i);
+      if (r == q * 4 + i && row < N) delta[hs + row] = t[i];
+      st[i] = active && row < N ? stats[hs + row] : f32x2{0.f, 0.f};
+    }
+  }
+  f32x4 dq[D / 16] = {};
+
+  float kreg[D / 16][4], vreg[D / 16][4];
+  fetch_block<T, D>(kreg, qkv + hq + E, 3 * E, 0, N);
+  fetch_block<T, D>(vreg, qkv + hq + 2 * E, 3 * E, 0, N);
+  for (int k0 = 0; k0 < N; k0 += kBlk) {
+    block_sync();
+    put_block<D>(sK, PK, kreg);
+    put_block<D>(sV, PV, vreg);
+    block_sync();
+    if (k0 + kBlk < N) {
+      fetch_block<T, D>(kreg, qkv + hq + E, 3 * E, k0 + kBlk, N);
+      fetch_block<T, D>(vreg, qkv + hq + 2 * E, 3 * E, k0 + kBlk, N);
+    }
+    if (!active) continue;
+    const int nt = min(4, (N - k0 + 15) >> 4);
+    f32x4 s4[4] = {}, ds4[4] = {};
+    strip_rk<D>(s4, a_q, sK, PK, nt, r, q);    // S
+    strip_rk<D>(ds4, a_do, sV, PV, nt, r, q);  // dP
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const bool row_live = row0 + q * 4 + i < N;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const bool live = row_live && j < nt && k0 + j * 16 + r < N;
+        const float p = p_from_stats(s4[j][i], st[i], c, live);
+        ds4[j][i] = p * (ds4[j][i] - dl[i]) * scale;
+      }
+    }
+    put_strip(strip, ds4, nt, r, q);
+    strip_out<D, false>(dq, strip, kStripP, 0, sK, PK, nt * 16, r, q);
+  }
+  if (active) {
+    const float one[4] = {1.f, 1.f, 1.f, 1.f};
+    store_strip<T, D>(dqkv + hq, 3 * E, dq, row0, N, one, r, q);
+  }
+}
+
+// Backward, key side. The wave's rows are KEYS, so its strips are S^T, dP^T:
+// row = key row0 + 4q + i, column = query q0 + 16j + r, and the statistics
+// and delta are one value per lane and query tile j. Images: Q (S^T: rk,
+// dK: kr; 72), dO (dP^T: rk, dV: kr; 72), four strips (P^T, then dS^T).
+template <typename T, int D>
+__global__ __launch_bounds__(256, 2) void k_attn_tiled_bwd_kv(
+    const T* __restrict__ qkv, const T* __restrict__ dout,
+    const f32x2* __restrict__ stats, const float* __restrict__ delta,
+    T* __restrict__ dqkv, int N, int H, int nblk, float scale) {
+  constexpr int PQ = 72;
+  __shared__ float sQ[kBlk * PQ];
+  __shared__ float sO[kBlk * PQ];
+  __shared__ float sS[kBlk * kStripP];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r = lane & 15, q = lane >> 4;
+  const TiledBlock w = tiled_block(H, nblk);
+  const size_t E = (size_t)H * D;
+  const size_t hq = (size_t)w.b * N * 3 * E + (size_t)w.h * D;
+  const size_t ho = (size_t)w.b * N * E + (size_t)w.h * D;
+  const size_t hs = ((size_t)w.b * H + w.h) * N;
+  const int row0 = w.blk * kBlk + wave * 16;
+  const bool active = row0 < N;
+  float* strip = sS + wave * 16 * kStripP;
+  const float c = scale * kLog2e;
+
+  float a_k[D / 4], a_v[D / 4];
+  load_a<T, D>(a_k, qkv + hq + E, 3 * E, row0 + r, N, q);
+  load_a<T, D>(a_v, qkv + hq + 2 * E, 3 * E, row0 + r, N, q);
+  f32x4 dk[D / 16] = {}, dv[D / 16] = {};
+
+  float qreg[D / 16][4], oreg[D / 16][4];
+  fetch_block<T, D>(qreg, qkv + hq, 3 * E, 0, N);
+  fetch_block<T, D>(oreg, dout + ho, E, 0, N);
+  for (int q0 = 0; q0 < N; q0 += kBlk) {
+    block_sync();
+    put_block<D>(sQ, PQ, qreg);
+    put_block<D>(sO, PQ, oreg);
+    block_sync();
+    if (q0 + kBlk < N) {
+      fetch_block<T, D>(qreg, qkv + hq, 3 * E, q0 + kBlk, N);
+      fetch_block<T, D>(oreg, dout + ho, E, q0 + kBlk, N);
+    }
+    if (!active) continue;
+    const int nt = min(4, (N - q0 + 15) >> 4);
+    f32x2 st[4];
+    float dl[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int col = q0 + j * 16 + r;
+      const bool in = j < nt && col < N;
+      st[j] = in ? stats[hs + col] : f32x2{0.f, 0.f};
+      dl[j] = in ? delta[hs + col] : 0.f;
+    }
+    f32x4 p4[4] = {}, ds4[4] = {};
+    strip_rk<D>(p4, a_k, sQ, PQ, nt, r, q);   // S^T
+    strip_rk<D>(ds4, a_v, sO, PQ, nt, r, q);  // dP^T
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const bool row_live = row0 + q * 4 + i < N;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const bool live = row_live && j < nt && q0 + j * 16 + r < N;
+        const float p = p_from_stats(p4[j][i], st[j], c, live);
+        p4[j][i] = p;
+        ds4[j][i] = p * (ds4[j][i] - dl[j]) * scale;
+      }
+    }
+    put_strip(strip, p4, nt, r, q);
+    strip_out<D, false>(dv, strip, kStripP, 0, sO, PQ, nt * 16, r, q);
+    put_strip(strip, ds4, nt, r, q);
+    strip_out<D, false>(dk, strip, kStripP, 0, sQ, PQ, nt * 16, r, q);
+  }
+  if (active) {
+    const float one[4] = {1.f, 1.f, 1.f, 1.f};
+    store_strip<T, D>(dqkv + hq + E, 3 * E, dk, row0, N, one, r, q);
+    store_strip<T, D>(dqkv + hq + 2 * E, 3 * E, dv, row0, N, one, r, q);
+  }
+}
+
 struct AttnDims {
   int64_t B, N, H, D;
 };
 
-// The argument check shared by attn_fwd and attn_bwd, complete before any
-// launch.
+// The argument check shared by the forward and backward launchers of both
+// families, complete before any launch.
 AttnDims attn_check_args(const char* who, const torch::Tensor& qkv,
-                         int64_t heads) {
+                         int64_t heads, int64_t max_n = kAttnMaxN) {
   TORCH_CHECK(qkv.defined() && qkv.is_cuda(), who, ": qkv must be on a GPU");
   const auto dt = qkv.scalar_type();
   TORCH_CHECK(dt == at::kFloat || dt == at::kBFloat16, who,
@@ -355,12 +720,37 @@ AttnDims attn_check_args(const char* who, const torch::Tensor& qkv,
   const int64_t D = qkv.size(2) / (3 * heads);
   TORCH_CHECK(D == 16 || D == 32 || D == 64, who,
               " supports head sizes 16, 32 and 64, got D = ", D);
-  TORCH_CHECK(N >= 1 && N <= kAttnMaxN, who, " supports 1 <= N <= ", kAttnMaxN,
+  TORCH_CHECK(N >= 1 && N <= max_n, who, " supports 1 <= N <= ", max_n,
               " tokens, got N = ", N);
-  TORCH_CHECK(B * heads <= INT32_MAX, who, ": B * heads exceeds the grid");
+  TORCH_CHECK(B * heads * ((N + kBlk - 1) / kBlk) <= INT32_MAX, who,
+              ": B * heads exceeds the grid");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16 == 0, who,
               ": qkv must be 16-byte aligned");
   return {B, N, heads, D};
+}
+
+// A [B, N, E] operand beside qkv (dout, out) and the forward's statistics.
+void attn_check_slab(const char* who, const char* name, const torch::Tensor& t,
+                     const torch::Tensor& qkv, const AttnDims& d) {
+  TORCH_CHECK(t.defined() && t.device() == qkv.device() &&
+                  t.scalar_type() == qkv.scalar_type(),
+              who, ": ", name, " must have qkv's dtype and device");
+  TORCH_CHECK(t.dim() == 3 && t.is_contiguous() && t.size(0) == d.B &&
+                  t.size(1) == d.N && t.size(2) == d.H * d.D,
+              who, ": ", name, " must be [B, N, E] = [", d.B, ", ", d.N, ", ",
+              d.H * d.D, "] and contiguous");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, who, ": ",
+              name, " must be 16-byte aligned");
+}
+void attn_check_stats(const char* who, const torch::Tensor& row_stats,
+                      const torch::Tensor& qkv, const AttnDims& d) {
+  TORCH_CHECK(row_stats.defined() && row_stats.device() == qkv.device() &&
+                  row_stats.scalar_type() == at::kFloat &&
+                  row_stats.is_contiguous() && row_stats.dim() == 4 &&
+                  row_stats.size(0) == d.B && row_stats.size(1) == d.H &&
+                  row_stats.size(2) == d.N && row_stats.size(3) == 2,
+              who, ": row_stats must be the forward's f32 [B, H, N, 2] = [",
+              d.B, ", ", d.H, ", ", d.N, ", 2] on qkv's device");
 }
 
 // A caller's preallocated result, checked, or a fresh one.
@@ -416,23 +806,8 @@ torch::Tensor attn_bwd(torch::Tensor dout, torch::Tensor qkv,
                        c10::optional<torch::Tensor> dqkv_) {
   const char* who = "attn_bwd";
   const AttnDims d = attn_check_args(who, qkv, heads);
-  TORCH_CHECK(dout.defined() && dout.device() == qkv.device() &&
-                  dout.scalar_type() == qkv.scalar_type(),
-              who, ": dout must have qkv's dtype and device");
-  TORCH_CHECK(dout.dim() == 3 && dout.is_contiguous() &&
-                  dout.size(0) == d.B && dout.size(1) == d.N &&
-                  dout.size(2) == d.H * d.D,
-              who, ": dout must be [B, N, E] = [", d.B, ", ", d.N, ", ",
-              d.H * d.D, "] and contiguous");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(dout.data_ptr()) % 16 == 0, who,
-              ": dout must be 16-byte aligned");
-  TORCH_CHECK(row_stats.defined() && row_stats.device() == qkv.device() &&
-                  row_stats.scalar_type() == at::kFloat &&
-                  row_stats.is_contiguous() && row_stats.dim() == 4 &&
-                  row_stats.size(0) == d.B && row_stats.size(1) == d.H &&
-                  row_stats.size(2) == d.N && row_stats.size(3) == 2,
-              who, ": row_stats must be attn_fwd's f32 [B, H, N, 2] = [", d.B,
-              ", ", d.H, ", ", d.N, ", 2] on qkv's device");
+  attn_check_slab(who, "dout", dout, qkv, d);
+  attn_check_stats(who, row_stats, qkv, d);
   auto dqkv = attn_result(who, "dqkv", dqkv_, qkv.sizes(), qkv.options());
   if (d.B == 0) return dqkv;
   const float scale = 1.f / std::sqrt((float)d.D);
@@ -443,6 +818,66 @@ torch::Tensor attn_bwd(torch::Tensor dout, torch::Tensor qkv,
                          0, cur_stream(), cdptr<scalar_t>(qkv),
                          cdptr<scalar_t>(dout), cdptr<float2>(row_stats),
                          dptr<scalar_t>(dqkv), (int)d.N, (int)d.H, scale);
+    });
+  });
+  HIP_OK(hipGetLastError());
+  return dqkv;
+}
+
+std::vector<torch::Tensor> attn_tiled_fwd(
+    torch::Tensor qkv, int64_t heads, c10::optional<torch::Tensor> out_,
+    c10::optional<torch::Tensor> row_stats_) {
+  const char* who = "attn_tiled_fwd";
+  const AttnDims d = attn_check_args(who, qkv, heads, kAttnTiledMaxN);
+  auto out = attn_result(who, "out", out_, {d.B, d.N, d.H * d.D},
+                         qkv.options());
+  auto stats = attn_result(who, "row_stats", row_stats_, {d.B, d.H, d.N, 2},
+                           qkv.options().dtype(at::kFloat));
+  if (d.B == 0) return {out, stats};
+  const float scale = 1.f / std::sqrt((float)d.D);
+  const int nblk = cdiv(d.N, kBlk);
+  DISPATCH_F32_BF16(qkv.scalar_type(), who, {
+    with_head_dim(d.D, [&](auto dd) {
+      constexpr int D = decltype(dd)::value;
+      hipLaunchKernelGGL((k_attn_tiled_fwd<scalar_t, D>),
+                         dim3(d.B * d.H * nblk), dim3(256), 0, cur_stream(),
+                         cdptr<scalar_t>(qkv), dptr<scalar_t>(out),
+                         dptr<f32x2>(stats), (int)d.N, (int)d.H, nblk, scale);
+    });
+  });
+  HIP_OK(hipGetLastError());
+  return {out, stats};
+}
+
+torch::Tensor attn_tiled_bwd(torch::Tensor dout, torch::Tensor qkv,
+                             torch::Tensor out, torch::Tensor row_stats,
+                             int64_t heads,
+                             c10::optional<torch::Tensor> dqkv_) {
+  const char* who = "attn_tiled_bwd";
+  const AttnDims d = attn_check_args(who, qkv, heads, kAttnTiledMaxN);
+  attn_check_slab(who, "dout", dout, qkv, d);
+  attn_check_slab(who, "out", out, qkv, d);
+  attn_check_stats(who, row_stats, qkv, d);
+  auto dqkv = attn_result(who, "dqkv", dqkv_, qkv.sizes(), qkv.options());
+  if (d.B == 0) return dqkv;
+  // rowsum(dO * O): written by the query-side kernel, read by the key-side one
+  auto delta = torch::empty({d.B, d.H, d.N}, qkv.options().dtype(at::kFloat));
+  const float scale = 1.f / std::sqrt((float)d.D);
+  const int nblk = cdiv(d.N, kBlk);
+  DISPATCH_F32_BF16(qkv.scalar_type(), who, {
+    with_head_dim(d.D, [&](auto dd) {
+      constexpr int D = decltype(dd)::value;
+      const dim3 grid(d.B * d.H * nblk);
+      hipLaunchKernelGGL((k_attn_tiled_bwd_q<scalar_t, D>), grid, dim3(256), 0,
+                         cur_stream(), cdptr<scalar_t>(qkv),
+                         cdptr<scalar_t>(dout), cdptr<scalar_t>(out),
+                         cdptr<f32x2>(row_stats), dptr<float>(delta),
+                         dptr<scalar_t>(dqkv), (int)d.N, (int)d.H, nblk, scale);
+      hipLaunchKernelGGL((k_attn_tiled_bwd_kv<scalar_t, D>), grid, dim3(256),
+                         0, cur_stream(), cdptr<scalar_t>(qkv),
+                         cdptr<scalar_t>(dout), cdptr<f32x2>(row_stats),
+                         cdptr<float>(delta), dptr<scalar_t>(dqkv), (int)d.N,
+                         (int)d.H, nblk, scale);
     });
   });
   HIP_OK(hipGetLastError());

@@ -116,20 +116,33 @@ struct CeFn : public torch::autograd::Function<CeFn> {
 };
 
 // Fused self-attention on the packed in-projection output. Saved for the
-// backward: qkv and the forward's row statistics, nothing else.
+// backward: qkv and the forward's row statistics, and above 64 tokens, where
+// the tiled kernels run, the output too (their delta comes from it).
 struct AttnFn : public torch::autograd::Function<AttnFn> {
+  static bool tiled(const torch::Tensor& qkv) {
+    return qkv.dim() == 3 && qkv.size(1) > 64;
+  }
+
   static torch::Tensor forward(AutogradContext* ctx, torch::Tensor qkv,
                                int64_t heads) {
-    auto outs = attn_fwd(qkv, heads);  // (out, row_stats)
-    ctx->save_for_backward({qkv, outs[1]});
     ctx->saved_data["heads"] = heads;
+    if (tiled(qkv)) {
+      auto outs = attn_tiled_fwd(qkv, heads);  // (out, row_stats)
+      ctx->save_for_backward({qkv, outs[1], outs[0]});
+      return outs[0];
+    }
+    auto outs = attn_fwd(qkv, heads);
+    ctx->save_for_backward({qkv, outs[1]});
     return outs[0];
   }
 
   static variable_list backward(AutogradContext* ctx, variable_list grads) {
     auto saved = ctx->get_saved_variables();
-    return {attn_bwd(grads[0].contiguous(), saved[0], saved[1],
-                     ctx->saved_data["heads"].toInt()),
+    const int64_t heads = ctx->saved_data["heads"].toInt();
+    auto dout = grads[0].contiguous();
+    return {tiled(saved[0])
+                ? attn_tiled_bwd(dout, saved[0], saved[2], saved[1], heads)
+                : attn_bwd(dout, saved[0], saved[1], heads),
             torch::Tensor()};
   }
 };

@@ -288,6 +288,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_bwd", &mi355x::attn_bwd, py::arg("dout"), py::arg("qkv"),
         py::arg("row_stats"), py::arg("heads"),
         py::arg("dqkv") = c10::nullopt);
+  m.def("attn_tiled_fwd", &mi355x::attn_tiled_fwd, py::arg("qkv"),
+        py::arg("heads"), py::arg("out") = c10::nullopt,
+        py::arg("row_stats") = c10::nullopt);
+  m.def("attn_tiled_bwd", &mi355x::attn_tiled_bwd, py::arg("dout"),
+        py::arg("qkv"), py::arg("out"), py::arg("row_stats"), py::arg("heads"),
+        py::arg("dqkv") = c10::nullopt);
   m.def("ln_fwd", &mi355x::ln_fwd, py::arg("x"), py::arg("weight"),
         py::arg("bias"), py::arg("eps"), py::arg("residual") = c10::nullopt,
         py::arg("y") = c10::nullopt, py::arg("row_stats") = c10::nullopt,

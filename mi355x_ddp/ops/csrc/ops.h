@@ -53,6 +53,21 @@ torch::Tensor attn_bwd(torch::Tensor dout, torch::Tensor qkv,
                        torch::Tensor row_stats, int64_t heads,
                        c10::optional<torch::Tensor> dqkv = c10::nullopt);
 
+// The tiled family of the same file: the same operands, layouts, checks and
+// arithmetic for 1 <= N <= 4096. A workgroup owns 64 rows and walks the other
+// side in blocks of 64 (online softmax in the forward). The backward is two
+// launches, dQ by query block and dK/dV by key block, without atomics; it
+// takes delta = rowsum(dO * O) from the forward's `out` [B, N, E], which the
+// caller therefore keeps.
+std::vector<torch::Tensor> attn_tiled_fwd(
+    torch::Tensor qkv, int64_t heads,
+    c10::optional<torch::Tensor> out = c10::nullopt,
+    c10::optional<torch::Tensor> row_stats = c10::nullopt);
+torch::Tensor attn_tiled_bwd(torch::Tensor dout, torch::Tensor qkv,
+                             torch::Tensor out, torch::Tensor row_stats,
+                             int64_t heads,
+                             c10::optional<torch::Tensor> dqkv = c10::nullopt);
+
 // Fused LayerNorm over the last dimension, optionally with the residual add
 // in front of it (layernorm_kernels.hip). Rows are the flattened leading
 // dimensions of a contiguous x; E = x.size(-1), E % 4 == 0, 4 <= E <= 2048;

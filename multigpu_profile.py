@@ -42,14 +42,14 @@ def load_train_objs(dataset_size: int = 2048):
     if kind == "tiny":
         shape = (3, 32, 32)
         model = _tiny_cnn()
-    elif kind == "vit":
-        from mi355x_ddp.models import vit_l_32
-        # the reference imports it but leaves it commented out (ref
-        # multigpu_profile.py:24); here it runs. MI355X_VIT_ATTENTION=hip
-        # takes the fused short-sequence attention kernels,
-        # MI355X_VIT_NORM=hip the fused LayerNorm kernels, MI355X_VIT_MLP=hip
-        # the tiled-GEMM MLP
-        model = vit_l_32(
+    elif kind in ("vit", "vit_b_16"):
+        from mi355x_ddp.models import vit_b_16, vit_l_32
+        # the reference imports vit_l_32 but leaves it commented out (ref
+        # multigpu_profile.py:24); here it runs, and vit_b_16 (197 tokens)
+        # beside it. MI355X_VIT_ATTENTION=hip takes the fused attention
+        # kernels, MI355X_VIT_NORM=hip the fused LayerNorm kernels,
+        # MI355X_VIT_MLP=hip the tiled-GEMM MLP
+        model = (vit_l_32 if kind == "vit" else vit_b_16)(
             attention=os.environ.get("MI355X_VIT_ATTENTION", "torch"),
             norm=os.environ.get("MI355X_VIT_NORM", "torch"),
             mlp=os.environ.get("MI355X_VIT_MLP", "torch"))

@@ -1,5 +1,6 @@
-"""Time the fused short-sequence self-attention against the torch path at the
-ViT-L/32 shape (B 32, H 16, N 50, D 64), forward plus backward, f32 and bf16:
+"""Time the fused self-attention against the torch path at the ViT-L/32 shape
+(B 32, H 16, N 50, D 64; `--shape B H N D` for another, such as ViT-B/16's
+32 12 197 64), forward plus backward, f32 and bf16:
 
   (a) ops.self_attention on the packed qkv  vs  F.scaled_dot_product_attention
       WITH the reshapes and transposes nn.MultiheadAttention does around it
@@ -63,11 +64,16 @@ def compare(pairs, iters, repeats):
 
 
 def main():
+    global B, H, N, D, E
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--json")
+    ap.add_argument("--shape", type=int, nargs=4, default=[B, H, N, D],
+                    metavar=("B", "H", "N", "D"))
     args = ap.parse_args()
+    B, H, N, D = args.shape
+    E = H * D
     assert torch.cuda.is_available(), "bench_attention needs a GPU"
     result = {"shape": {"B": B, "H": H, "N": N, "D": D},
               "iters": args.iters, "repeats": args.repeats}
