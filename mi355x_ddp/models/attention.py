@@ -8,6 +8,10 @@ initialisation, so state dicts and snapshots interchange in both directions.
 Its forward is `ops.linear` -> `ops.self_attention` -> `ops.linear`: the
 attention kernel reads the in-projection's packed [B, N, 3E] output where it
 lies and writes [B, N, E] for the out-projection, so no per-head copy exists.
+`matrix="bf16"` selects the wide bf16 MFMA kernels (`ops.self_attention`'s
+argument of that name: bf16 activations or bf16 autocast, heads of 32 or 64);
+the default `"f32"` keeps the exact-fp32 products. Parameters do not depend
+on it.
 """
 
 from __future__ import annotations
@@ -19,11 +23,14 @@ from .. import ops
 
 
 class HipSelfAttention(nn.Module):
-    def __init__(self, embed_dim: int, num_heads: int):
+    def __init__(self, embed_dim: int, num_heads: int, matrix: str = "f32"):
         super().__init__()
         if embed_dim % num_heads:
             raise ValueError("embed_dim must be divisible by num_heads")
+        if matrix not in ("f32", "bf16"):
+            raise ValueError(f"matrix must be 'f32' or 'bf16', got {matrix!r}")
         self.embed_dim, self.num_heads = embed_dim, num_heads
+        self.matrix = matrix
         self.in_proj_weight = nn.Parameter(
             torch.empty(3 * embed_dim, embed_dim))
         self.in_proj_bias = nn.Parameter(torch.empty(3 * embed_dim))
@@ -37,5 +44,5 @@ class HipSelfAttention(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """x: [B, N, E] -> [B, N, E]."""
         qkv = ops.linear(x, self.in_proj_weight, self.in_proj_bias)
-        y = ops.self_attention(qkv, self.num_heads)
+        y = ops.self_attention(qkv, self.num_heads, self.matrix)
         return ops.linear(y, self.out_proj.weight, self.out_proj.bias)

@@ -16,9 +16,11 @@ adds, GELU, GELU' and the bias gradients in their epilogues). LayerNorm
 is `norm="torch"` (`nn.LayerNorm`, the default) or `norm="hip"`
 (`HipLayerNorm`: the fused row kernels, with the residual add in front of
 `ln_2` folded into it). Attention is `attention="torch"`
-(`nn.MultiheadAttention`, the default) or `attention="hip"`
+(`nn.MultiheadAttention`, the default), `attention="hip"`
 (`HipSelfAttention`: the fused attention kernels, any N up to 4096 tokens,
-heads of 16, 32 or 64). The three switches are independent, and every
+heads of 16, 32 or 64, exact-fp32 products) or `attention="hip-bf16"`
+(`HipSelfAttention(matrix="bf16")`: the wide bf16 MFMA kernels, for bf16
+activations or bf16 autocast, heads of 32 or 64). The three switches are independent, and every
 combination has the same parameters under the same names. In
 `VisionTransformer` and `EncoderBlock`, where `mlp` already is the MLP's
 width, the switch is spelled `mlp_impl`; `vit_l_32`, `vit_b_16` and `vit_tiny`
@@ -48,17 +50,18 @@ class EncoderBlock(nn.Module):
                  attention: str = "torch", norm: str = "torch",
                  mlp_impl: str = "torch"):
         super().__init__()
-        if attention not in ("torch", "hip"):
-            raise ValueError(f"attention must be 'torch' or 'hip', "
-                             f"got {attention!r}")
+        if attention not in ("torch", "hip", "hip-bf16"):
+            raise ValueError(f"attention must be 'torch', 'hip' or "
+                             f"'hip-bf16', got {attention!r}")
         if mlp_impl not in ("torch", "hip"):
             raise ValueError(f"mlp_impl (mlp= of vit_l_32 / vit_tiny) must be "
                              f"'torch' or 'hip', got {mlp_impl!r}")
-        self.hip_attention = attention == "hip"
+        self.hip_attention = attention != "torch"
         self.hip_norm = norm == "hip"
         self.ln_1 = _layer_norm(norm, hidden)
         if self.hip_attention:
-            self.self_attention = HipSelfAttention(hidden, heads)
+            self.self_attention = HipSelfAttention(
+                hidden, heads, "bf16" if attention == "hip-bf16" else "f32")
         else:
             self.self_attention = nn.MultiheadAttention(hidden, heads,
                                                         batch_first=True)

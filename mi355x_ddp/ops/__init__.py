@@ -138,7 +138,8 @@ def linear_gelu(x: torch.Tensor, w: torch.Tensor,
 # ---------------------------------------------------------------------------
 # Fused self-attention (csrc/attention_kernels.hip)
 # ---------------------------------------------------------------------------
-def self_attention(qkv: torch.Tensor, heads: int) -> torch.Tensor:
+def self_attention(qkv: torch.Tensor, heads: int,
+                   matrix: str = "f32") -> torch.Tensor:
     """softmax(Q K^T / sqrt(D)) V per head, on the packed in-projection
     output: `qkv` is [B, N, 3*E] with columns [0,E) Q, [E,2E) K, [2E,3E) V
     and head h at columns h*D.. of each (E = heads*D); the result is
@@ -149,12 +150,26 @@ def self_attention(qkv: torch.Tensor, heads: int) -> torch.Tensor:
     one workgroup per (batch, head) runs the whole head out of LDS; above,
     the tiled kernels walk the keys in blocks of 64 with an online softmax
     and the backward additionally keeps the output. Under autocast the input
-    is cast to the autocast dtype, as `linear` does. The CPU path is the
-    formula in plain torch ops, the kernels' mirror."""
+    is cast to the autocast dtype, as `linear` does.
+
+    `matrix` names the matrix instruction of the five products. "f32" (the
+    default) is the exact-fp32 path above, whatever the storage.
+    "bf16" runs them on the wide bf16 MFMA for every N up to 4096 (D 32 or
+    64): it needs bf16 `qkv` (after the autocast cast; anything else raises
+    ValueError), keeps the softmax, the statistics and every accumulator in
+    fp32 and rounds P and dS to bf16 once, on their way into the second
+    product. The CPU path is the formula in plain torch ops, the kernels'
+    mirror, for either value."""
+    if matrix not in ("f32", "bf16"):
+        raise ValueError(f"self_attention: matrix must be 'f32' or 'bf16', "
+                         f"got {matrix!r}")
     if qkv.is_cuda:
         if torch.is_autocast_enabled("cuda"):
             qkv = qkv.to(torch.get_autocast_dtype("cuda"))
-        return ext().attention_autograd(qkv, heads)
+        if matrix == "bf16" and qkv.dtype != torch.bfloat16:
+            raise ValueError(f"self_attention: matrix='bf16' needs bf16 qkv "
+                             f"(or bf16 autocast), got {qkv.dtype}")
+        return ext().attention_autograd(qkv, heads, matrix)
     B, N, E3 = qkv.shape
     if heads < 1 or E3 % (3 * heads):
         raise ValueError("self_attention: the last dimension must be "

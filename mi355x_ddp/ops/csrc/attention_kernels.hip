@@ -8,8 +8,9 @@
 //                    reciprocal of the row's sum of exponentials
 //   dqkv [B, N, 3E]  the three gradients in qkv's own layout
 //
-// Two kernel families: the short one described here, and below it the tiled
-// one for up to 4096 tokens (k_attn_tiled_*), which shares its helpers.
+// Three kernel families: the short one described here, below it the tiled
+// one for up to 4096 tokens (k_attn_tiled_*), which shares its helpers, and
+// last the bf16-only one on the wide bf16 MFMA (k_attn_bf16_*).
 //
 // 1 <= N <= 64, D in {16, 32, 64}; no mask, no dropout. A whole (batch, head)
 // problem is smaller than one flash-attention tile, so ONE workgroup of four
@@ -699,6 +700,426 @@ __global__ __launch_bounds__(256, 2) void k_attn_tiled_bwd_kv(
   }
 }
 
+// ===========================================================================
+// The bf16 family: bf16 storage only, D in {32, 64}, 1 <= N <= 4096, all five
+// products on v_mfma_f32_16x16x32_bf16. The work split, grid, two backward
+// launches, layouts and masking are the tiled family's; the operands are not.
+//
+// Lane maps of the wide MFMA (r = lane & 15, q = lane >> 4): A[m = r][k =
+// 8q + e], B[k = 8q + e][n = r], e < 8; C/D col = r, row = 4q + reg. The
+// contraction only needs A and B to agree on which index a slot (q, e) means.
+//
+// The wave's own 16 rows are always the B operand (n = r), 16 bytes per lane
+// and step from global memory. Every product has the walked side as A (m):
+//   first   S^T = K_blk Q_own^T (fwd, bwd_q), dP^T = V_blk dO_own^T (bwd_q),
+//           S = Q_blk K_own^T, dP = dO_blk V_own^T (bwd_kv): A is one
+//           ds_read_b128 from a straight [64][D] image. Lane (r, q) of
+//           fragment j then holds walked rows 16j + 4q .. + 3 of own row r.
+//   second  O^T = V^T P^T, dQ^T = K^T dS^T, dV^T = dO^T P, dK^T = Q^T dS:
+//           the contraction runs over the walked rows. Fragments 2t, 2t + 1,
+//           rounded and packed, ARE the lane's B operand of wide step t with
+//           slot e < 4 = walked row 32t + 4q + e, e >= 4 = 32t + 16 + 4q +
+//           e - 4; A comes from a transposed [D][64] image with two
+//           ds_read_b64 at those offsets. P and dS never touch LDS.
+// Every result lands as own row r, columns 16u + 4q .. + 3 of lane (r, q):
+// the softmax statistics of a query are per lane column in fwd and bwd_q
+// (two cross-lane steps), and a result row is stored 8 bytes per lane.
+//
+// Images. Straight: pitch D/2 + 4 words (4 * odd: the 16 lanes of one
+// quarter of a ds_read_b128 cover all 64 banks). Transposed: two adjacent
+// walked rows interleaved into words while storing, pitch 36 words: the 32
+// lanes of half a ds_read_b64 (r, q & 1) hit words 36 r + 2 (q & 1) + const,
+// all 64 banks once.
+// ===========================================================================
+using bf16_t = __hip_bfloat16;
+using u32x4 = __attribute__((ext_vector_type(4))) uint32_t;
+using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
+constexpr int kPT = 36;  // words per row of a transposed image
+
+// Two floats to two bf16, round to nearest even (v_cvt_pk_bf16_f32).
+__device__ __forceinline__ uint32_t bf16_pack(float lo, float hi) {
+  const bf16x2 p = {(__bf16)lo, (__bf16)hi};
+  return __builtin_bit_cast(uint32_t, p);
+}
+// Fragments 2t and 2t + 1 as the B operand of wide step t.
+__device__ __forceinline__ u32x4 pack_pair(f32x4 x, f32x4 y) {
+  return u32x4{bf16_pack(x[0], x[1]), bf16_pack(x[2], x[3]),
+               bf16_pack(y[0], y[1]), bf16_pack(y[2], y[3])};
+}
+__device__ __forceinline__ f32x4 mfma32(u32x4 a, u32x4 b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+      __builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0,
+      0);
+}
+// Over the four lanes that share r (one own row).
+__device__ __forceinline__ float col4_max(float v, int lane) {
+  v = fmaxf(v, from_lane(v, lane ^ 16));
+  return fmaxf(v, from_lane(v, lane ^ 32));
+}
+__device__ __forceinline__ float col4_sum(float v, int lane) {
+  v += from_lane(v, lane ^ 16);
+  return v + from_lane(v, lane ^ 32);
+}
+
+// The lane's B operand of its own row for a contraction over D.
+template <int D>
+__device__ __forceinline__ void load_own(u32x4 b[D / 32], const bf16_t* src,
+                                         size_t ld, int row, int N, int q) {
+#pragma unroll
+  for (int s = 0; s < D / 32; ++s) {
+    b[s] = u32x4{0u, 0u, 0u, 0u};
+    if (row < N)
+      b[s] = *reinterpret_cast<const u32x4*>(src + (size_t)row * ld + 32 * s +
+                                             8 * q);
+  }
+}
+
+// A walked block of 64 rows x D: a thread moves the same 8 columns (chunk c)
+// of the adjacent rows 2p, 2p + 1, first into registers (rows >= N zero),
+// then into the straight image as loaded and/or the transposed one with the
+// two rows interleaved. Four chunks per row and wave, 16 row pairs per wave:
+// 64-byte global segments, and the interleaved stores of a wave meet 32
+// banks (two-way, as k_gemm_tile's). At D = 32 waves 2 and 3 have no chunk.
+template <int D>
+struct Walked {
+  static constexpr int PS = D / 2 + 4;  // words per row of a straight image
+  int c, p;
+  __device__ __forceinline__ Walked() {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    c = 4 * (wave % (D / 32)) + (lane & 3);
+    p = 16 * (wave / (D / 32)) + (lane >> 2);
+  }
+  __device__ __forceinline__ void fetch(u32x4 v[2], const bf16_t* src,
+                                        size_t ld, int row0, int N) const {
+    v[0] = v[1] = u32x4{0u, 0u, 0u, 0u};
+    const int row = row0 + 2 * p;
+    if (p < 32 && row < N)
+      v[0] = *reinterpret_cast<const u32x4*>(src + (size_t)row * ld + 8 * c);
+    if (p < 32 && row + 1 < N)
+      v[1] =
+          *reinterpret_cast<const u32x4*>(src + (size_t)(row + 1) * ld + 8 * c);
+  }
+  template <bool STRAIGHT, bool TRANSPOSED>
+  __device__ __forceinline__ void put(uint32_t* simg, uint32_t* timg,
+                                      const u32x4 v[2]) const {
+    if (p >= 32) return;
+    if constexpr (STRAIGHT) {
+      *reinterpret_cast<u32x4*>(&simg[(2 * p) * PS + 4 * c]) = v[0];
+      *reinterpret_cast<u32x4*>(&simg[(2 * p + 1) * PS + 4 * c]) = v[1];
+    }
+    if constexpr (TRANSPOSED) {
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {
+        const uint32_t lo = v[0][w], hi = v[1][w];
+        timg[(8 * c + 2 * w) * kPT + p] = (lo & 0xffffu) | (hi << 16);
+        timg[(8 * c + 2 * w + 1) * kPT + p] = (lo >> 16) | (hi & 0xffff0000u);
+      }
+    }
+  }
+};
+
+// acc[j] += simg rows 16j .. 16j + 15 (A) . the own rows (B), j < nt.
+template <int D>
+__device__ __forceinline__ void first_product(f32x4 acc[4],
+                                              const uint32_t* simg,
+                                              const u32x4 b[D / 32], int nt,
+                                              int r, int q) {
+  constexpr int PS = Walked<D>::PS;
+#pragma unroll
+  for (int s = 0; s < D / 32; ++s) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (j < nt)
+        acc[j] = mfma32(*reinterpret_cast<const u32x4*>(
+                            &simg[(16 * j + r) * PS + 16 * s + 4 * q]),
+                        b[s], acc[j]);
+  }
+}
+// acc[u] += timg columns 16u .. 16u + 15 (A) . the packed fragments (B) over
+// the wide steps t < nw, the image read in the fragments' row order.
+template <int D>
+__device__ __forceinline__ void second_product(f32x4 acc[D / 16],
+                                               const uint32_t* timg,
+                                               const u32x4 b[2], int nw, int r,
+                                               int q) {
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+    if (t < nw) {
+#pragma unroll
+      for (int u = 0; u < D / 16; ++u) {
+        const uint32_t* at = &timg[(16 * u + r) * kPT + 16 * t + 2 * q];
+        const u32x2 lo = *reinterpret_cast<const u32x2*>(at);
+        const u32x2 hi = *reinterpret_cast<const u32x2*>(at + 8);
+        acc[u] = mfma32(u32x4{lo[0], lo[1], hi[0], hi[1]}, b[t], acc[u]);
+      }
+    }
+}
+// Own row `row`, columns 16u + 4q .. + 3, times mul, rounded once.
+template <int D>
+__device__ __forceinline__ void store_own(bf16_t* dst, size_t ld,
+                                          const f32x4 acc[D / 16], int row,
+                                          int N, float mul, int q) {
+  if (row >= N) return;
+#pragma unroll
+  for (int u = 0; u < D / 16; ++u)
+    *reinterpret_cast<u32x2*>(dst + (size_t)row * ld + 16 * u + 4 * q) =
+        u32x2{bf16_pack(acc[u][0] * mul, acc[u][1] * mul),
+              bf16_pack(acc[u][2] * mul, acc[u][3] * mul)};
+}
+
+// Forward. Images: K straight, V transposed. P is rounded to bf16 once, on
+// its way into O^T += V^T P^T, and l sums the ROUNDED P: a row of out is an
+// exact convex combination of V rows.
+template <int D>
+__global__ __launch_bounds__(256, D == 64 ? 3 : 4) void k_attn_bf16_fwd(
+    const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
+    f32x2* __restrict__ stats, int N, int H, int nblk, float scale) {
+  __shared__ __attribute__((aligned(16))) uint32_t sK[kBlk * Walked<D>::PS];
+  __shared__ __attribute__((aligned(16))) uint32_t sVt[D * kPT];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r = lane & 15, q = lane >> 4;
+  const TiledBlock w = tiled_block(H, nblk);
+  const size_t E = (size_t)H * D;
+  const bf16_t* src = qkv + (size_t)w.b * N * 3 * E + (size_t)w.h * D;
+  const int row0 = w.blk * kBlk + wave * 16;
+  const bool active = row0 < N;  // the others only stage
+  const float c = scale * kLog2e;
+
+  u32x4 b_q[D / 32];
+  load_own<D>(b_q, src, 3 * E, row0 + r, N, q);
+  float m = -INFINITY, l = 0.f;  // of query row0 + r, alike in its four lanes
+  f32x4 o[D / 16] = {};
+
+  const Walked<D> wk;
+  u32x4 kreg[2], vreg[2];
+  wk.fetch(kreg, src + E, 3 * E, 0, N);
+  wk.fetch(vreg, src + 2 * E, 3 * E, 0, N);
+  for (int k0 = 0; k0 < N; k0 += kBlk) {
+    block_sync();  // the previous block's reads are done
+    wk.template put<true, false>(sK, nullptr, kreg);
+    wk.template put<false, true>(nullptr, sVt, vreg);
+    block_sync();
+    if (k0 + kBlk < N) {
+      wk.fetch(kreg, src + E, 3 * E, k0 + kBlk, N);
+      wk.fetch(vreg, src + 2 * E, 3 * E, k0 + kBlk, N);
+    }
+    if (!active) continue;
+    const int rows = min(kBlk, N - k0);
+    const int nt = (rows + 15) >> 4, nw = (rows + 31) >> 5;
+    f32x4 s4[4] = {};
+    first_product<D>(s4, sK, b_q, nt, r, q);
+    // lane (r, q), fragment j, word i: query row0 + r, key k0 + 16j + 4q + i
+    float mb = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        if (j >= nt || k0 + 16 * j + 4 * q + i >= N) s4[j][i] = -INFINITY;
+        mb = fmaxf(mb, s4[j][i]);
+      }
+    }
+    // finite: key k0 exists. From m = -inf the factor is exp2(-inf) = 0.
+    const float mn = fmaxf(m, col4_max(mb, lane));
+    const float f = __builtin_amdgcn_exp2f((m - mn) * c);
+    m = mn;
+    u32x4 pk[2];
+    float sum = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+      for (int i = 0; i < 4; i += 2) {
+        const uint32_t two =
+            bf16_pack(__builtin_amdgcn_exp2f((s4[j][i] - mn) * c),
+                      __builtin_amdgcn_exp2f((s4[j][i + 1] - mn) * c));
+        pk[j >> 1][(j & 1) * 2 + (i >> 1)] = two;
+        sum += as_f32(two << 16) + as_f32(two & 0xffff0000u);
+      }
+    }
+    l = l * f + col4_sum(sum, lane);
+#pragma unroll
+    for (int u = 0; u < D / 16; ++u) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) o[u][i] *= f;
+    }
+    second_product<D>(o, sVt, pk, nw, r, q);
+  }
+  if (active) {
+    const int row = row0 + r;
+    const float il = 1.f / l;
+    if (q == 0 && row < N)
+      stats[((size_t)w.b * H + w.h) * N + row] = f32x2{m, il};
+    store_own<D>(out + (size_t)w.b * N * E + (size_t)w.h * D, E, o, row, N, il,
+                 q);
+  }
+}
+
+// Backward, query side. Images: K straight (S^T) and transposed (dQ^T), V
+// straight (dP^T). P comes back from the statistics in f32 and dS is rounded
+// once, on its way into dQ^T += K^T dS^T. Leaves delta[b, h, row] for bwd_kv.
+template <int D>
+__global__ __launch_bounds__(256, 3) void k_attn_bf16_bwd_q(
+    const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
+    const bf16_t* __restrict__ out, const f32x2* __restrict__ stats,
+    float* __restrict__ delta, bf16_t* __restrict__ dqkv, int N, int H,
+    int nblk, float scale) {
+  __shared__ __attribute__((aligned(16))) uint32_t sK[kBlk * Walked<D>::PS];
+  __shared__ __attribute__((aligned(16))) uint32_t sKt[D * kPT];
+  __shared__ __attribute__((aligned(16))) uint32_t sV[kBlk * Walked<D>::PS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r = lane & 15, q = lane >> 4;
+  const TiledBlock w = tiled_block(H, nblk);
+  const size_t E = (size_t)H * D;
+  const size_t hq = (size_t)w.b * N * 3 * E + (size_t)w.h * D;
+  const size_t ho = (size_t)w.b * N * E + (size_t)w.h * D;
+  const size_t hs = ((size_t)w.b * H + w.h) * N;
+  const int row0 = w.blk * kBlk + wave * 16, row = row0 + r;
+  const bool active = row0 < N;
+  const float c = scale * kLog2e;
+
+  u32x4 b_q[D / 32], b_do[D / 32];
+  load_own<D>(b_q, qkv + hq, 3 * E, row, N, q);
+  load_own<D>(b_do, dout + ho, E, row, N, q);
+  // delta = the diagonal of O dO^T, by the MFMA steps that form dP^T = V dO^T
+  // with O's rows in V's place: where a row has one key (O = V) delta equals
+  // dP bit for bit and dS is exactly 0. Element (r, r) sits in lane (r, r / 4),
+  // word r % 4; the row's other three lanes fetch it from there.
+  float dl;
+  {
+    u32x4 a_o[D / 32];
+    load_own<D>(a_o, out + ho, E, row, N, q);
+    f32x4 t = {};
+#pragma unroll
+    for (int s = 0; s < D / 32; ++s) t = mfma32(a_o[s], b_do[s], t);
+    const int i = r & 3;
+    const float d = i == 0 ? t[0] : i == 1 ? t[1] : i == 2 ? t[2] : t[3];
+    dl = from_lane(d, (r >> 2) * 16 + r);
+    if (q == (r >> 2) && row < N) delta[hs + row] = d;
+  }
+  const f32x2 st = active && row < N ? stats[hs + row] : f32x2{0.f, 0.f};
+  f32x4 dq[D / 16] = {};
+
+  const Walked<D> wk;
+  u32x4 kreg[2], vreg[2];
+  wk.fetch(kreg, qkv + hq + E, 3 * E, 0, N);
+  wk.fetch(vreg, qkv + hq + 2 * E, 3 * E, 0, N);
+  for (int k0 = 0; k0 < N; k0 += kBlk) {
+    block_sync();
+    wk.template put<true, true>(sK, sKt, kreg);
+    wk.template put<true, false>(sV, nullptr, vreg);
+    block_sync();
+    if (k0 + kBlk < N) {
+      wk.fetch(kreg, qkv + hq + E, 3 * E, k0 + kBlk, N);
+      wk.fetch(vreg, qkv + hq + 2 * E, 3 * E, k0 + kBlk, N);
+    }
+    if (!active) continue;
+    const int rows = min(kBlk, N - k0);
+    const int nt = (rows + 15) >> 4, nw = (rows + 31) >> 5;
+    f32x4 s4[4] = {}, ds4[4] = {};
+    first_product<D>(s4, sK, b_q, nt, r, q);    // S^T
+    first_product<D>(ds4, sV, b_do, nt, r, q);  // dP^T
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const bool live = row < N && j < nt && k0 + 16 * j + 4 * q + i < N;
+        const float p = p_from_stats(s4[j][i], st, c, live);
+        ds4[j][i] = p * (ds4[j][i] - dl) * scale;
+      }
+    }
+    const u32x4 pk[2] = {pack_pair(ds4[0], ds4[1]), pack_pair(ds4[2], ds4[3])};
+    second_product<D>(dq, sKt, pk, nw, r, q);
+  }
+  if (active) store_own<D>(dqkv + hq, 3 * E, dq, row, N, 1.f, q);
+}
+
+// Backward, key side. The wave's rows are KEYS: lane (r, q) of fragment j
+// holds queries q0 + 16j + 4q .. + 3 of key row0 + r, so the statistics and
+// delta are four words per fragment, staged per block beside the images
+// (Q and dO, each straight and transposed). P is used in f32 for dS and a
+// rounded copy feeds dV^T += dO^T P; dS is rounded into dK^T += Q^T dS.
+template <int D>
+__global__ __launch_bounds__(256, D == 64 ? 2 : 3) void k_attn_bf16_bwd_kv(
+    const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
+    const f32x2* __restrict__ stats, const float* __restrict__ delta,
+    bf16_t* __restrict__ dqkv, int N, int H, int nblk, float scale) {
+  __shared__ __attribute__((aligned(16))) uint32_t sQ[kBlk * Walked<D>::PS];
+  __shared__ __attribute__((aligned(16))) uint32_t sQt[D * kPT];
+  __shared__ __attribute__((aligned(16))) uint32_t sO[kBlk * Walked<D>::PS];
+  __shared__ __attribute__((aligned(16))) uint32_t sOt[D * kPT];
+  __shared__ __attribute__((aligned(16))) float sSt[3][kBlk];  // m, 1/l, delta
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r = lane & 15, q = lane >> 4;
+  const TiledBlock w = tiled_block(H, nblk);
+  const size_t E = (size_t)H * D;
+  const size_t hq = (size_t)w.b * N * 3 * E + (size_t)w.h * D;
+  const size_t ho = (size_t)w.b * N * E + (size_t)w.h * D;
+  const size_t hs = ((size_t)w.b * H + w.h) * N;
+  const int row0 = w.blk * kBlk + wave * 16, row = row0 + r;
+  const bool active = row0 < N;
+  const float c = scale * kLog2e;
+
+  u32x4 b_k[D / 32], b_v[D / 32];
+  load_own<D>(b_k, qkv + hq + E, 3 * E, row, N, q);
+  load_own<D>(b_v, qkv + hq + 2 * E, 3 * E, row, N, q);
+  f32x4 dk[D / 16] = {}, dv[D / 16] = {};
+
+  const Walked<D> wk;
+  u32x4 qreg[2], oreg[2];
+  f32x2 streg = {0.f, 0.f};  // wave 0: the statistics of query q0 + lane
+  float dlreg = 0.f;
+  auto fetch_stats = [&](int q0) {
+    const bool in = wave == 0 && q0 + lane < N;
+    streg = in ? stats[hs + q0 + lane] : f32x2{0.f, 0.f};
+    dlreg = in ? delta[hs + q0 + lane] : 0.f;
+  };
+  wk.fetch(qreg, qkv + hq, 3 * E, 0, N);
+  wk.fetch(oreg, dout + ho, E, 0, N);
+  fetch_stats(0);
+  for (int q0 = 0; q0 < N; q0 += kBlk) {
+    block_sync();
+    wk.template put<true, true>(sQ, sQt, qreg);
+    wk.template put<true, true>(sO, sOt, oreg);
+    if (wave == 0)
+      sSt[0][lane] = streg[0], sSt[1][lane] = streg[1], sSt[2][lane] = dlreg;
+    block_sync();
+    if (q0 + kBlk < N) {
+      wk.fetch(qreg, qkv + hq, 3 * E, q0 + kBlk, N);
+      wk.fetch(oreg, dout + ho, E, q0 + kBlk, N);
+      fetch_stats(q0 + kBlk);
+    }
+    if (!active) continue;
+    const int rows = min(kBlk, N - q0);
+    const int nt = (rows + 15) >> 4, nw = (rows + 31) >> 5;
+    f32x4 p4[4] = {}, ds4[4] = {};
+    first_product<D>(p4, sQ, b_k, nt, r, q);   // S
+    first_product<D>(ds4, sO, b_v, nt, r, q);  // dP
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const f32x4 m4 = *reinterpret_cast<const f32x4*>(&sSt[0][16 * j + 4 * q]);
+      const f32x4 il4 =
+          *reinterpret_cast<const f32x4*>(&sSt[1][16 * j + 4 * q]);
+      const f32x4 dl4 =
+          *reinterpret_cast<const f32x4*>(&sSt[2][16 * j + 4 * q]);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const bool live = row < N && j < nt && q0 + 16 * j + 4 * q + i < N;
+        const float p =
+            p_from_stats(p4[j][i], f32x2{m4[i], il4[i]}, c, live);
+        p4[j][i] = p;
+        ds4[j][i] = p * (ds4[j][i] - dl4[i]) * scale;
+      }
+    }
+    const u32x4 pp[2] = {pack_pair(p4[0], p4[1]), pack_pair(p4[2], p4[3])};
+    second_product<D>(dv, sOt, pp, nw, r, q);
+    const u32x4 pd[2] = {pack_pair(ds4[0], ds4[1]), pack_pair(ds4[2], ds4[3])};
+    second_product<D>(dk, sQt, pd, nw, r, q);
+  }
+  if (active) {
+    store_own<D>(dqkv + hq + E, 3 * E, dk, row, N, 1.f, q);
+    store_own<D>(dqkv + hq + 2 * E, 3 * E, dv, row, N, 1.f, q);
+  }
+}
+
 struct AttnDims {
   int64_t B, N, H, D;
 };
@@ -879,6 +1300,95 @@ torch::Tensor attn_tiled_bwd(torch::Tensor dout, torch::Tensor qkv,
                          cdptr<float>(delta), dptr<scalar_t>(dqkv), (int)d.N,
                          (int)d.H, nblk, scale);
     });
+  });
+  HIP_OK(hipGetLastError());
+  return dqkv;
+}
+
+namespace {
+
+// The bf16 family's own limits, complete before any launch.
+AttnDims attn_bf16_check_args(const char* who, const torch::Tensor& qkv,
+                              int64_t heads) {
+  TORCH_CHECK(qkv.defined() && qkv.is_cuda(), who, ": qkv must be on a GPU");
+  TORCH_CHECK(qkv.scalar_type() == at::kBFloat16, who,
+              ": storage must be bf16 (the wide MFMA has no f32 form), got ",
+              qkv.scalar_type());
+  TORCH_CHECK(qkv.dim() == 3 && qkv.is_contiguous(), who,
+              ": qkv must be [B, N, 3*E] and contiguous");
+  TORCH_CHECK(heads >= 1 && qkv.size(2) % (3 * heads) == 0, who,
+              ": the last dimension (", qkv.size(2),
+              ") must be 3 * heads * D with heads = ", heads);
+  const int64_t B = qkv.size(0), N = qkv.size(1);
+  const int64_t D = qkv.size(2) / (3 * heads);
+  TORCH_CHECK(D == 32 || D == 64, who,
+              " supports head sizes 32 and 64, got D = ", D);
+  TORCH_CHECK(N >= 1 && N <= kAttnTiledMaxN, who, " supports 1 <= N <= ",
+              kAttnTiledMaxN, " tokens, got N = ", N);
+  TORCH_CHECK(B * heads * ((N + kBlk - 1) / kBlk) <= INT32_MAX, who,
+              ": B * heads exceeds the grid");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16 == 0, who,
+              ": qkv must be 16-byte aligned");
+  return {B, N, heads, D};
+}
+
+template <typename F>
+void with_wide_head_dim(int64_t D, F&& f) {
+  if (D == 32) f(std::integral_constant<int, 32>{});
+  else f(std::integral_constant<int, 64>{});
+}
+
+}  // namespace
+
+std::vector<torch::Tensor> attn_bf16_fwd(
+    torch::Tensor qkv, int64_t heads, c10::optional<torch::Tensor> out_,
+    c10::optional<torch::Tensor> row_stats_) {
+  const char* who = "attn_bf16_fwd";
+  const AttnDims d = attn_bf16_check_args(who, qkv, heads);
+  auto out = attn_result(who, "out", out_, {d.B, d.N, d.H * d.D},
+                         qkv.options());
+  auto stats = attn_result(who, "row_stats", row_stats_, {d.B, d.H, d.N, 2},
+                           qkv.options().dtype(at::kFloat));
+  if (d.B == 0) return {out, stats};
+  const float scale = 1.f / std::sqrt((float)d.D);
+  const int nblk = cdiv(d.N, kBlk);
+  with_wide_head_dim(d.D, [&](auto dd) {
+    constexpr int D = decltype(dd)::value;
+    hipLaunchKernelGGL((k_attn_bf16_fwd<D>), dim3(d.B * d.H * nblk), dim3(256),
+                       0, cur_stream(), cdptr<bf16_t>(qkv), dptr<bf16_t>(out),
+                       dptr<f32x2>(stats), (int)d.N, (int)d.H, nblk, scale);
+  });
+  HIP_OK(hipGetLastError());
+  return {out, stats};
+}
+
+torch::Tensor attn_bf16_bwd(torch::Tensor dout, torch::Tensor qkv,
+                            torch::Tensor out, torch::Tensor row_stats,
+                            int64_t heads,
+                            c10::optional<torch::Tensor> dqkv_) {
+  const char* who = "attn_bf16_bwd";
+  const AttnDims d = attn_bf16_check_args(who, qkv, heads);
+  attn_check_slab(who, "dout", dout, qkv, d);
+  attn_check_slab(who, "out", out, qkv, d);
+  attn_check_stats(who, row_stats, qkv, d);
+  auto dqkv = attn_result(who, "dqkv", dqkv_, qkv.sizes(), qkv.options());
+  if (d.B == 0) return dqkv;
+  // diag(O dO^T): written by the query-side kernel, read by the key-side one
+  auto delta = torch::empty({d.B, d.H, d.N}, qkv.options().dtype(at::kFloat));
+  const float scale = 1.f / std::sqrt((float)d.D);
+  const int nblk = cdiv(d.N, kBlk);
+  with_wide_head_dim(d.D, [&](auto dd) {
+    constexpr int D = decltype(dd)::value;
+    const dim3 grid(d.B * d.H * nblk);
+    hipLaunchKernelGGL((k_attn_bf16_bwd_q<D>), grid, dim3(256), 0,
+                       cur_stream(), cdptr<bf16_t>(qkv), cdptr<bf16_t>(dout),
+                       cdptr<bf16_t>(out), cdptr<f32x2>(row_stats),
+                       dptr<float>(delta), dptr<bf16_t>(dqkv), (int)d.N,
+                       (int)d.H, nblk, scale);
+    hipLaunchKernelGGL((k_attn_bf16_bwd_kv<D>), grid, dim3(256), 0,
+                       cur_stream(), cdptr<bf16_t>(qkv), cdptr<bf16_t>(dout),
+                       cdptr<f32x2>(row_stats), cdptr<float>(delta),
+                       dptr<bf16_t>(dqkv), (int)d.N, (int)d.H, nblk, scale);
   });
   HIP_OK(hipGetLastError());
   return dqkv;

@@ -147,6 +147,26 @@ struct AttnFn : public torch::autograd::Function<AttnFn> {
   }
 };
 
+// The same on the bf16 wide-MFMA kernels, for every N they take. Saved for the
+// backward: qkv, the row statistics and the output.
+struct AttnBf16Fn : public torch::autograd::Function<AttnBf16Fn> {
+  static torch::Tensor forward(AutogradContext* ctx, torch::Tensor qkv,
+                               int64_t heads) {
+    ctx->saved_data["heads"] = heads;
+    auto outs = attn_bf16_fwd(qkv, heads);  // (out, row_stats)
+    ctx->save_for_backward({qkv, outs[1], outs[0]});
+    return outs[0];
+  }
+
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    auto saved = ctx->get_saved_variables();
+    const int64_t heads = ctx->saved_data["heads"].toInt();
+    return {attn_bf16_bwd(grads[0].contiguous(), saved[0], saved[2], saved[1],
+                          heads),
+            torch::Tensor()};
+  }
+};
+
 // Fused LayerNorm. Saved for the backward: the input, the forward's row
 // statistics and the weight; the output is not kept.
 struct LayerNormFn : public torch::autograd::Function<LayerNormFn> {
@@ -293,8 +313,13 @@ torch::Tensor ce_autograd(torch::Tensor y, torch::Tensor t) {
   return CeFn::apply(y, t);
 }
 
-torch::Tensor attention_autograd(torch::Tensor qkv, int64_t heads) {
-  return AttnFn::apply(qkv, heads);
+torch::Tensor attention_autograd(torch::Tensor qkv, int64_t heads,
+                                 const std::string& matrix) {
+  TORCH_CHECK(matrix == "f32" || matrix == "bf16",
+              "attention_autograd: matrix must be 'f32' or 'bf16', got '",
+              matrix, "'");
+  return matrix == "bf16" ? AttnBf16Fn::apply(qkv, heads)
+                          : AttnFn::apply(qkv, heads);
 }
 
 }  // namespace mi355x

@@ -18,7 +18,8 @@ torch::Tensor linear_autograd(torch::Tensor x, torch::Tensor w,
                               c10::optional<torch::Tensor> b);
 torch::Tensor mse_autograd(torch::Tensor y, torch::Tensor t);
 torch::Tensor ce_autograd(torch::Tensor y, torch::Tensor t);
-torch::Tensor attention_autograd(torch::Tensor qkv, int64_t heads);
+torch::Tensor attention_autograd(torch::Tensor qkv, int64_t heads,
+                                 const std::string& matrix);
 torch::Tensor layer_norm_autograd(torch::Tensor x, torch::Tensor weight,
                                   torch::Tensor bias, double eps);
 std::vector<torch::Tensor> add_layer_norm_autograd(torch::Tensor x,
@@ -294,6 +295,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_tiled_bwd", &mi355x::attn_tiled_bwd, py::arg("dout"),
         py::arg("qkv"), py::arg("out"), py::arg("row_stats"), py::arg("heads"),
         py::arg("dqkv") = c10::nullopt);
+  m.def("attn_bf16_fwd", &mi355x::attn_bf16_fwd, py::arg("qkv"),
+        py::arg("heads"), py::arg("out") = c10::nullopt,
+        py::arg("row_stats") = c10::nullopt);
+  m.def("attn_bf16_bwd", &mi355x::attn_bf16_bwd, py::arg("dout"),
+        py::arg("qkv"), py::arg("out"), py::arg("row_stats"), py::arg("heads"),
+        py::arg("dqkv") = c10::nullopt);
   m.def("ln_fwd", &mi355x::ln_fwd, py::arg("x"), py::arg("weight"),
         py::arg("bias"), py::arg("eps"), py::arg("residual") = c10::nullopt,
         py::arg("y") = c10::nullopt, py::arg("row_stats") = c10::nullopt,
@@ -463,7 +470,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mse_autograd", &mi355x::mse_autograd);
   m.def("ce_autograd", &mi355x::ce_autograd);
   m.def("attention_autograd", &mi355x::attention_autograd, py::arg("qkv"),
-        py::arg("heads"));
+        py::arg("heads"), py::arg("matrix") = "f32");
   m.def("layer_norm_autograd", &mi355x::layer_norm_autograd, py::arg("x"),
         py::arg("weight"), py::arg("bias"), py::arg("eps"));
   m.def("add_layer_norm_autograd", &mi355x::add_layer_norm_autograd,

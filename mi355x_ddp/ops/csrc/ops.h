@@ -68,6 +68,22 @@ torch::Tensor attn_tiled_bwd(torch::Tensor dout, torch::Tensor qkv,
                              int64_t heads,
                              c10::optional<torch::Tensor> dqkv = c10::nullopt);
 
+// The bf16 family of the same file: the tiled family's operands, layouts and
+// work split for bf16 storage ONLY, D in {32, 64}, 1 <= N <= 4096, with all
+// five products on v_mfma_f32_16x16x32_bf16 (f32 accumulators, softmax and
+// statistics). P and dS are rounded to bf16 once, on their way into the
+// second product; row_stats' 1/l is that of the rounded P. f32 storage, any
+// other D or N, a non-contiguous or misplaced operand are refused before a
+// launch; B == 0 launches nothing.
+std::vector<torch::Tensor> attn_bf16_fwd(
+    torch::Tensor qkv, int64_t heads,
+    c10::optional<torch::Tensor> out = c10::nullopt,
+    c10::optional<torch::Tensor> row_stats = c10::nullopt);
+torch::Tensor attn_bf16_bwd(torch::Tensor dout, torch::Tensor qkv,
+                            torch::Tensor out, torch::Tensor row_stats,
+                            int64_t heads,
+                            c10::optional<torch::Tensor> dqkv = c10::nullopt);
+
 // Fused LayerNorm over the last dimension, optionally with the residual add
 // in front of it (layernorm_kernels.hip). Rows are the flattened leading
 // dimensions of a contiguous x; E = x.size(-1), E % 4 == 0, 4 <= E <= 2048;

@@ -12,6 +12,10 @@ times; prints and optionally writes one JSON with the median and the
 min..max of the per-call microseconds.
 
     python tools/bench_attention.py [--json profiles/attention_r10a.json]
+
+`--matrix bf16` times bf16 storage only and adds the wide bf16 MFMA kernels
+(`matrix="bf16"`, key "hip-bf16") as a third version, alternating with the
+f32-MFMA path ("hip") and the library ("torch") in the same call.
 """
 import argparse
 import json
@@ -71,13 +75,18 @@ def main():
     ap.add_argument("--json")
     ap.add_argument("--shape", type=int, nargs=4, default=[B, H, N, D],
                     metavar=("B", "H", "N", "D"))
+    ap.add_argument("--matrix", choices=("f32", "bf16"), default="f32")
     args = ap.parse_args()
     B, H, N, D = args.shape
     E = H * D
+    wide = args.matrix == "bf16"
     assert torch.cuda.is_available(), "bench_attention needs a GPU"
     result = {"shape": {"B": B, "H": H, "N": N, "D": D},
-              "iters": args.iters, "repeats": args.repeats}
+              "iters": args.iters, "repeats": args.repeats,
+              "matrix": args.matrix}
     for dtype, name in ((torch.float32, "f32"), (torch.bfloat16, "bf16")):
+        if wide and dtype != torch.bfloat16:
+            continue
         torch.manual_seed(0)
         qkv = torch.randn(B, N, 3 * E, device=DEV, dtype=dtype,
                           requires_grad=True)
@@ -93,6 +102,9 @@ def main():
         a, b = ops.self_attention(qkv, H), torch_core(qkv)
         assert (a - b).abs().max() <= (2e-2 if dtype == torch.bfloat16
                                        else 1e-5), (a - b).abs().max()
+        if wide:
+            a = ops.self_attention(qkv, H, matrix="bf16")
+            assert (a - b).abs().max() <= 2e-2, (a - b).abs().max()
         hip = HipSelfAttention(E, H).to(DEV, dtype)
         mha = nn.MultiheadAttention(E, H, batch_first=True).to(DEV, dtype)
         mha.load_state_dict(hip.state_dict())
@@ -104,15 +116,20 @@ def main():
                 f(x).backward(dout)
             return run
 
+        cores = {"hip": core(lambda t: ops.self_attention(t, H)),
+                 "torch": core(torch_core)}
+        modules = {"hip": module(hip),
+                   "torch": module(
+                       lambda t: mha(t, t, t, need_weights=False)[0])}
+        if wide:
+            hip_wide = HipSelfAttention(E, H, matrix="bf16").to(DEV, dtype)
+            hip_wide.load_state_dict(hip.state_dict())
+            cores = {"hip-bf16": core(
+                lambda t: ops.self_attention(t, H, matrix="bf16")), **cores}
+            modules = {"hip-bf16": module(hip_wide), **modules}
         result[name] = {
-            "core": compare(
-                {"hip": core(lambda t: ops.self_attention(t, H)),
-                 "torch": core(torch_core)}, args.iters, args.repeats),
-            "module": compare(
-                {"hip": module(hip),
-                 "torch": module(
-                     lambda t: mha(t, t, t, need_weights=False)[0])},
-                args.iters, args.repeats)}
+            "core": compare(cores, args.iters, args.repeats),
+            "module": compare(modules, args.iters, args.repeats)}
     line = json.dumps(result)
     print(line)
     if args.json:

@@ -1,7 +1,8 @@
 """Time ViT-L/32 training steps through the native engine (multi-bucket
 reducer + fused SGD; the model the reference imports but leaves commented
 out — multigpu_profile.py:24). MI355X_AUTOCAST_BF16=1 for bf16,
-MI355X_VIT_ATTENTION=hip for the fused short-sequence attention kernels,
+MI355X_VIT_ATTENTION=hip for the fused short-sequence attention kernels
+(hip-bf16, with bf16 autocast, for the wide bf16 MFMA ones),
 MI355X_VIT_NORM=hip for the fused LayerNorm kernels, MI355X_VIT_MLP=hip for
 the tiled-GEMM MLP."""
 import os
