@@ -2,8 +2,9 @@
 
 Every op has two paths:
 - device tensors -> the hand-written CDNA4 HIP kernels in `mi355x_ddp._C`
-  (MFMA-tiled linear, the tiled-GEMM MLP, CE/MSE, fused SGD / momentum SGD / AdamW, global
-  grad-norm clipping, bucket copies). If the extension
+  (MFMA-tiled linear, the tiled-GEMM MLP, CE/MSE, the class-index
+  cross-entropy with label smoothing and ignore_index, fused SGD / momentum
+  SGD / AdamW, global grad-norm clipping, bucket copies). If the extension
   is missing on a GPU host this layer raises — there is NO silent eager
   fallback on the GPU.
 - CPU tensors -> plain PyTorch reference implementations, used by the
@@ -258,6 +259,69 @@ def cross_entropy(output: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     if output.is_cuda:
         return ext().ce_autograd(output, target.to(output.dtype))
     return F.cross_entropy(output, target.to(output.dtype))
+
+
+def cross_entropy_index(logits: torch.Tensor, labels: torch.Tensor,
+                        label_smoothing: float = 0.0,
+                        ignore_index: int = -100,
+                        reduction: str = "mean") -> torch.Tensor:
+    """F.cross_entropy(logits, labels, label_smoothing=..., ignore_index=...,
+    reduction=...) for integer class labels without class weights, on kernels
+    of its own (csrc/loss_kernels.hip).
+
+    `logits` is [..., C], fp32 or bf16; `labels` is int64 or int32 with the
+    leading shape; `reduction` is "mean", "sum" or "none". The result is fp32:
+    a scalar, or the leading shape for "none". Rows whose label is
+    `ignore_index` contribute nothing and "mean" divides by the number of the
+    others, so with every row ignored it is NaN, as in torch. Other dtypes, a
+    device or shape mismatch, `label_smoothing` outside [0, 1] and an unknown
+    reduction raise ValueError on either device.
+
+    On the GPU the forward reads the logits once and the backward reads them
+    once and stores dlogits once; what is kept between them is two floats per
+    row. Under autocast the logits are NOT cast: the kernels widen bf16 on
+    load and compute in fp32, which gives the number a cast would give;
+    dlogits is rounded once to the logits' dtype. The loss is summed in a
+    fixed order without atomics: run to run the same bits. The logits must be
+    contiguous after the flatten and their storage 16-byte aligned.
+
+    Nothing is read back to the host, so the call can be captured into a
+    graph. The price: a label that is neither `ignore_index` nor in [0, C)
+    cannot raise. It is never used as an address; that row's loss and its row
+    of dlogits are NaN, the row counts as non-ignored and the other rows'
+    gradients are unaffected (torch asserts on the device instead).
+
+    `cross_entropy` keeps its own routing: integer targets given to it still
+    go through one-hot probabilities and negative ones still raise. Moving
+    that branch here is a later decision. The CPU path is F.cross_entropy."""
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"cross_entropy_index: logits must be float32 or "
+                         f"bfloat16, got {logits.dtype}")
+    if labels.dtype not in (torch.int64, torch.int32):
+        raise ValueError(f"cross_entropy_index: labels must be int64 or "
+                         f"int32, got {labels.dtype}")
+    if labels.device != logits.device:
+        raise ValueError(f"cross_entropy_index: logits on {logits.device}, "
+                         f"labels on {labels.device}")
+    if logits.dim() < 1 or logits.shape[-1] < 1 \
+            or labels.shape != logits.shape[:-1]:
+        raise ValueError(f"cross_entropy_index: labels {tuple(labels.shape)} "
+                         f"do not match logits {tuple(logits.shape)}")
+    if not 0.0 <= label_smoothing <= 1.0:
+        raise ValueError(f"cross_entropy_index: label_smoothing must be in "
+                         f"[0, 1], got {label_smoothing}")
+    if reduction not in ("mean", "sum", "none"):
+        raise ValueError(f"cross_entropy_index: reduction must be 'mean', "
+                         f"'sum' or 'none', got {reduction!r}")
+    if logits.is_cuda:
+        return ext().cei_autograd(logits.contiguous(), labels.contiguous(),
+                                  label_smoothing, ignore_index, reduction)
+    C = logits.shape[-1]
+    loss = F.cross_entropy(logits.reshape(-1, C).float(),
+                           labels.reshape(-1).long(),
+                           ignore_index=ignore_index, reduction=reduction,
+                           label_smoothing=label_smoothing)
+    return loss.reshape(labels.shape) if reduction == "none" else loss
 
 
 def mse_loss(output: torch.Tensor, target: torch.Tensor) -> torch.Tensor:

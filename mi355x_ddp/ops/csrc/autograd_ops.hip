@@ -115,6 +115,42 @@ struct CeFn : public torch::autograd::Function<CeFn> {
   }
 };
 
+// Cross-entropy on class indices. Saved for the backward: the logits, the
+// labels, row_stats [B, 2] and the device scalar inv_count; there is no
+// [B, C] f32 tensor. The incoming gradient is read by the kernel when it is
+// f32 on the device (the scalar seed, or one value per row for "none");
+// anything else is multiplied in afterwards. Nothing is read back.
+struct CeiFn : public torch::autograd::Function<CeiFn> {
+  static torch::Tensor forward(AutogradContext* ctx, torch::Tensor logits,
+                               torch::Tensor labels, double label_smoothing,
+                               int64_t ignore_index, std::string reduction) {
+    auto outs = cei_fwd(logits, labels, label_smoothing, ignore_index,
+                        reduction);  // (loss, row_stats, inv_count)
+    ctx->save_for_backward({logits, labels, outs[1], outs[2]});
+    ctx->saved_data["label_smoothing"] = label_smoothing;
+    ctx->saved_data["ignore_index"] = ignore_index;
+    ctx->saved_data["reduction"] = reduction;
+    return outs[0];
+  }
+
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    auto saved = ctx->get_saved_variables();
+    const double eps = ctx->saved_data["label_smoothing"].toDouble();
+    const int64_t ignore = ctx->saved_data["ignore_index"].toInt();
+    const std::string red = ctx->saved_data["reduction"].toStringRef();
+    const auto& g0 = grads[0];
+    const bool fold = g0.defined() && g0.is_cuda() &&
+                      g0.scalar_type() == at::kFloat &&
+                      (red == "none" || g0.numel() == 1);
+    auto dy = cei_bwd(fold ? c10::optional<torch::Tensor>(g0.contiguous())
+                           : c10::nullopt,
+                      saved[0], saved[1], saved[2], saved[3], eps, ignore, red);
+    if (!fold) dy = dy * (red == "none" ? g0.unsqueeze(-1) : g0);
+    return {dy, torch::Tensor(), torch::Tensor(), torch::Tensor(),
+            torch::Tensor()};
+  }
+};
+
 // Fused self-attention on the packed in-projection output. Saved for the
 // backward: qkv and the forward's row statistics, and above 64 tokens, where
 // the tiled kernels run, the output too (their delta comes from it).
@@ -311,6 +347,13 @@ torch::Tensor mse_autograd(torch::Tensor y, torch::Tensor t) {
 
 torch::Tensor ce_autograd(torch::Tensor y, torch::Tensor t) {
   return CeFn::apply(y, t);
+}
+
+torch::Tensor cei_autograd(torch::Tensor logits, torch::Tensor labels,
+                           double label_smoothing, int64_t ignore_index,
+                           const std::string& reduction) {
+  return CeiFn::apply(logits, labels, label_smoothing, ignore_index,
+                      reduction);
 }
 
 torch::Tensor attention_autograd(torch::Tensor qkv, int64_t heads,

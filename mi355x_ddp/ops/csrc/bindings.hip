@@ -18,6 +18,9 @@ torch::Tensor linear_autograd(torch::Tensor x, torch::Tensor w,
                               c10::optional<torch::Tensor> b);
 torch::Tensor mse_autograd(torch::Tensor y, torch::Tensor t);
 torch::Tensor ce_autograd(torch::Tensor y, torch::Tensor t);
+torch::Tensor cei_autograd(torch::Tensor logits, torch::Tensor labels,
+                           double label_smoothing, int64_t ignore_index,
+                           const std::string& reduction);
 torch::Tensor attention_autograd(torch::Tensor qkv, int64_t heads,
                                  const std::string& matrix);
 torch::Tensor layer_norm_autograd(torch::Tensor x, torch::Tensor weight,
@@ -343,6 +346,30 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ce_bwd", &mi355x::ce_bwd, py::arg("probs"), py::arg("t"),
         py::arg("tsum"), py::arg("grad_scale"),
         py::arg("gout") = c10::nullopt);
+  m.def(
+      "cei_fwd",
+      [](torch::Tensor logits, torch::Tensor labels, double label_smoothing,
+         int64_t ignore_index, const std::string& reduction,
+         c10::optional<torch::Tensor> row_stats,
+         c10::optional<torch::Tensor> workspace) {
+        auto outs = mi355x::cei_fwd(logits, labels, label_smoothing,
+                                    ignore_index, reduction, row_stats,
+                                    workspace);
+        return py::make_tuple(outs[0], outs[1], outs[2]);
+      },
+      py::arg("logits"), py::arg("labels"), py::arg("label_smoothing") = 0.0,
+      py::arg("ignore_index") = -100, py::arg("reduction") = "mean",
+      py::arg("row_stats") = c10::nullopt,
+      py::arg("workspace") = c10::nullopt);
+  m.def("cei_bwd", &mi355x::cei_bwd, py::arg("grad"), py::arg("logits"),
+        py::arg("labels"), py::arg("row_stats"), py::arg("inv_count"),
+        py::arg("label_smoothing") = 0.0, py::arg("ignore_index") = -100,
+        py::arg("reduction") = "mean", py::arg("dlogits") = c10::nullopt);
+  m.def("cei_plan", [](int64_t B, int64_t C) {
+    const auto p = mi355x::cei_plan(B, C);
+    return py::make_tuple(p[0], p[1]);
+  });
+  m.def("cei_grid_cap", &mi355x::cei_grid_cap);
   m.def("mse_fwd", &mi355x::mse_fwd);
   m.def("mse_bwd", &mi355x::mse_bwd, py::arg("y"), py::arg("t"),
         py::arg("grad_scale"), py::arg("gout") = c10::nullopt);
@@ -469,6 +496,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("w"), py::arg("bias") = c10::nullopt);
   m.def("mse_autograd", &mi355x::mse_autograd);
   m.def("ce_autograd", &mi355x::ce_autograd);
+  m.def("cei_autograd", &mi355x::cei_autograd, py::arg("logits"),
+        py::arg("labels"), py::arg("label_smoothing") = 0.0,
+        py::arg("ignore_index") = -100, py::arg("reduction") = "mean");
   m.def("attention_autograd", &mi355x::attention_autograd, py::arg("qkv"),
         py::arg("heads"), py::arg("matrix") = "f32");
   m.def("layer_norm_autograd", &mi355x::layer_norm_autograd, py::arg("x"),

@@ -3,7 +3,8 @@
 // (toy_fused_fwd_bwd, toy_multistep*) toy_kernels.hip, and for the
 // flat-bucket optimizers optim_kernels.hip, for the fused self-attention
 // attention_kernels.hip, for the fused LayerNorm layernorm_kernels.hip, for
-// the tiled GEMMs gemm_kernels.hip; bound to Python in bindings.hip.
+// the tiled GEMMs gemm_kernels.hip, for the class-index cross-entropy
+// loss_kernels.hip; bound to Python in bindings.hip.
 #pragma once
 #include <torch/extension.h>
 #include <cstdint>
@@ -151,6 +152,37 @@ std::vector<torch::Tensor> ce_fwd(torch::Tensor y, torch::Tensor t);
 torch::Tensor ce_bwd(torch::Tensor probs, torch::Tensor t,
                      torch::Tensor tsum, double grad_scale,
                      c10::optional<torch::Tensor> gout = c10::nullopt);
+
+// Cross-entropy on integer class labels with label smoothing, ignore_index
+// and reduction "mean" | "sum" | "none" (loss_kernels.hip): F.cross_entropy's
+// semantics for class indices without class weights. logits [..., C]
+// contiguous, 16-byte aligned, f32 or bf16, C >= 1; labels int64 or int32,
+// contiguous, of the leading shape; label_smoothing in [0, 1]. Anything else
+// is refused before a launch; no rows launches nothing. Nothing is read back
+// to the host. A label that is neither ignore_index nor in [0, C) is never
+// used as an address: that row's loss and dlogits row are NaN and it counts
+// as non-ignored.
+// cei_fwd returns (loss f32 [] or [...], row_stats f32 [B, 2] = (row max,
+//   1 / sum exp(y - max)), inv_count f32 [1] = 1 or 1 / #non-ignored rows).
+//   workspace is f32 [B, S, 4] with S = cei_plan(B, C)[0].
+// cei_bwd returns dlogits, rounded once to the logits' dtype. grad is the
+//   incoming gradient as a contiguous f32 device tensor, one value ("mean",
+//   "sum") or one per row ("none"); without it the gradient of the loss
+//   itself. Loss, count and dlogits are the same bits run to run.
+// cei_plan: (S, L), the column segments per row and their length, a function
+//   of (B, C) alone. cei_grid_cap: the cap on the row kernels' grid.
+std::vector<torch::Tensor> cei_fwd(
+    torch::Tensor logits, torch::Tensor labels, double label_smoothing,
+    int64_t ignore_index, const std::string& reduction,
+    c10::optional<torch::Tensor> row_stats = c10::nullopt,
+    c10::optional<torch::Tensor> workspace = c10::nullopt);
+torch::Tensor cei_bwd(c10::optional<torch::Tensor> grad, torch::Tensor logits,
+                      torch::Tensor labels, torch::Tensor row_stats,
+                      torch::Tensor inv_count, double label_smoothing,
+                      int64_t ignore_index, const std::string& reduction,
+                      c10::optional<torch::Tensor> dlogits = c10::nullopt);
+std::vector<int64_t> cei_plan(int64_t B, int64_t C);
+int64_t cei_grid_cap();
 
 // MSE (reference multinode_torchrun.py:46). Returns loss[scalar].
 torch::Tensor mse_fwd(torch::Tensor y, torch::Tensor t);

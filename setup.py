@@ -22,6 +22,7 @@ ext = CUDAExtension(
         "mi355x_ddp/ops/csrc/attention_kernels.hip",
         "mi355x_ddp/ops/csrc/layernorm_kernels.hip",
         "mi355x_ddp/ops/csrc/gemm_kernels.hip",
+        "mi355x_ddp/ops/csrc/loss_kernels.hip",
         "mi355x_ddp/ops/csrc/rccl_comm.hip",
         "mi355x_ddp/ops/csrc/p2p_mesh.hip",
         "mi355x_ddp/ops/csrc/reducer_core.hip",
