@@ -5,3 +5,4 @@ from .vit import (vit_b_16, vit_l_32, vit_tiny,  # noqa: F401
 from .attention import HipSelfAttention  # noqa: F401
 from .layernorm import HipLayerNorm  # noqa: F401
 from .mlp import HipMlp  # noqa: F401
+from .batchnorm import HipBatchNorm2d  # noqa: F401

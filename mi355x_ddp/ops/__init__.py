@@ -222,6 +222,77 @@ def add_layer_norm(x: torch.Tensor, residual: torch.Tensor,
 
 
 # ---------------------------------------------------------------------------
+# Fused BatchNorm (+ residual add) (+ ReLU) (csrc/batchnorm_kernels.hip)
+# ---------------------------------------------------------------------------
+def batch_norm_act(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
+                   running_mean: torch.Tensor, running_var: torch.Tensor, *,
+                   residual: Optional[torch.Tensor] = None, act: str = "relu",
+                   training: bool = True, momentum: float = 0.1,
+                   eps: float = 1e-5,
+                   num_batches_tracked: Optional[torch.Tensor] = None):
+    """z = act(batch_norm(x) + residual) over the channel dimension, `act`
+    "relu" or "none", `residual` optional and only with "relu": BN, BN+ReLU
+    and BN+add+ReLU, each three launches forward and three backward on the
+    GPU, with the ReLU mask read back from the saved output.
+
+    `x` is [R, C] (channels last) or [N, C, H, W]. A 4-D input is used in its
+    channels-last form: a view when it already is channels-last, otherwise
+    ONE `.contiguous(memory_format=torch.channels_last)` copy (and one of the
+    residual); the 4-D result is channels-last. C must be a multiple of 4 up
+    to 4096, the storage fp32 or bf16 (other inputs raise), the arithmetic is
+    fp32. Under autocast `x` and `residual` keep their dtype (torch's policy
+    for batch norm, unlike `layer_norm`); `weight`, `bias` and the running
+    statistics go to the kernels as fp32.
+
+    In training the batch statistics are used, `running_mean`/`running_var`
+    are updated in place (unbiased variance, `(1-momentum)*old +
+    momentum*new`) and `num_batches_tracked`, when given, is incremented on
+    the device by the same launch, so a captured step needs none of its own.
+    With `training=False` the running statistics are used in one launch;
+    gradients are then not supported and asking for them raises. Statistics
+    and the weight and bias gradients are summed in a fixed order without
+    atomics: run to run the same bits. The CPU path is F.batch_norm, add,
+    relu."""
+    if act not in ("relu", "none"):
+        raise ValueError(f"batch_norm_act: act must be 'relu' or 'none', "
+                         f"got {act!r}")
+    if residual is not None and act != "relu":
+        raise ValueError("batch_norm_act: a residual needs act='relu'")
+    if x.dim() not in (2, 4):
+        raise ValueError(f"batch_norm_act: x must be [R, C] or [N, C, H, W], "
+                         f"got {tuple(x.shape)}")
+    if residual is not None and residual.shape != x.shape:
+        raise ValueError(f"batch_norm_act: residual {tuple(residual.shape)} "
+                         f"does not match x {tuple(x.shape)}")
+    if not x.is_cuda:
+        y = F.batch_norm(x, running_mean, running_var, weight, bias, training,
+                         momentum, eps)
+        if training and num_batches_tracked is not None:
+            num_batches_tracked += 1
+        if residual is not None:
+            y = y + residual
+        return F.relu(y) if act == "relu" else y
+
+    def rows(t):
+        if t.dim() == 2:
+            return t.contiguous()
+        t = t.contiguous(memory_format=torch.channels_last)
+        return t.permute(0, 2, 3, 1).reshape(-1, t.shape[1]).contiguous()
+
+    rm, rv = running_mean.float(), running_var.float()
+    z = ext().batch_norm_act_autograd(
+        rows(x), weight.float(), bias.float(), rm, rv,
+        None if residual is None else rows(residual), act == "relu", training,
+        momentum, eps, num_batches_tracked)
+    if training and running_mean.dtype != torch.float32:  # rm, rv are copies
+        running_mean.copy_(rm), running_var.copy_(rv)
+    if x.dim() == 2:
+        return z
+    N, C, H, W = x.shape
+    return z.view(N, H, W, C).permute(0, 3, 1, 2)
+
+
+# ---------------------------------------------------------------------------
 # Losses (reference: CE at single_gpu.py:24, MSE at multinode_torchrun.py:46;
 # both take float probability/value targets of the same shape as the output)
 # ---------------------------------------------------------------------------

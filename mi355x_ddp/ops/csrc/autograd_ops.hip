@@ -247,6 +247,45 @@ struct AddLayerNormFn : public torch::autograd::Function<AddLayerNormFn> {
   }
 };
 
+// z = act(batch_norm(x) + residual) in training mode. Saved for the backward:
+// x, col_stats, the weight and, with ReLU, the output z, whose sign is the
+// mask; no mask tensor exists. The running statistics and the batch counter
+// are updated in place by the forward's second launch. Every tensor argument
+// is a defined tensor: without a residual (add false) or a counter (count
+// false) the caller passes a placeholder that is not looked at.
+struct BatchNormActFn : public torch::autograd::Function<BatchNormActFn> {
+  static torch::Tensor forward(AutogradContext* ctx, torch::Tensor x,
+                               torch::Tensor residual, torch::Tensor weight,
+                               torch::Tensor bias, torch::Tensor running_mean,
+                               torch::Tensor running_var,
+                               torch::Tensor batches, bool add, bool count,
+                               bool relu, double momentum, double eps) {
+    auto opt = [](bool given, const torch::Tensor& t) {
+      return given ? c10::optional<torch::Tensor>(t) : c10::nullopt;
+    };
+    auto outs = bn_fwd(x, weight, bias, running_mean, running_var,
+                       /*training=*/true, momentum, eps, relu,
+                       opt(add, residual),
+                       opt(count, batches));  // (z, col_stats)
+    if (relu) ctx->save_for_backward({x, outs[1], weight, outs[0]});
+    else ctx->save_for_backward({x, outs[1], weight});
+    ctx->saved_data["add"] = add;
+    return outs[0];
+  }
+
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    auto saved = ctx->get_saved_variables();
+    const bool add = ctx->saved_data["add"].toBool();
+    auto g = bn_bwd(grads[0].contiguous(), saved[0], saved[1], saved[2],
+                    saved.size() > 3 ? c10::optional<torch::Tensor>(saved[3])
+                                     : c10::nullopt,
+                    add);  // (dx, dgamma, dbeta[, dresidual])
+    return {g[0], add ? g[3] : torch::Tensor(), g[1], g[2], torch::Tensor(),
+            torch::Tensor(), torch::Tensor(), torch::Tensor(), torch::Tensor(),
+            torch::Tensor(), torch::Tensor(), torch::Tensor()};
+  }
+};
+
 // The two GEMMs that turn the gradient arriving at h into the gradients of a
 // linear layer's input, weight and bias; what is not needed is not computed.
 variable_list linear_grads(AutogradContext* ctx, const torch::Tensor& dh,
@@ -334,6 +373,31 @@ std::vector<torch::Tensor> add_layer_norm_autograd(torch::Tensor x,
                                                    torch::Tensor bias,
                                                    double eps) {
   return AddLayerNormFn::apply(x, residual, weight, bias, eps);
+}
+
+torch::Tensor batch_norm_act_autograd(
+    torch::Tensor x, torch::Tensor weight, torch::Tensor bias,
+    torch::Tensor running_mean, torch::Tensor running_var,
+    c10::optional<torch::Tensor> residual, bool relu, bool training,
+    double momentum, double eps,
+    c10::optional<torch::Tensor> num_batches_tracked) {
+  if (training)
+    return BatchNormActFn::apply(
+        x, residual.has_value() ? *residual : x, weight, bias, running_mean,
+        running_var,
+        num_batches_tracked.has_value() ? *num_batches_tracked : running_mean,
+        residual.has_value(), num_batches_tracked.has_value(), relu, momentum,
+        eps);
+  // evaluation: one launch from the running statistics, and no backward
+  const bool wants_grad =
+      torch::GradMode::is_enabled() &&
+      (x.requires_grad() || weight.requires_grad() || bias.requires_grad() ||
+       (residual.has_value() && residual->requires_grad()));
+  TORCH_CHECK(!wants_grad,
+              "batch_norm_act: gradients in evaluation mode (training=False) "
+              "are not supported; run under torch.no_grad()");
+  return bn_fwd(x, weight, bias, running_mean, running_var, false, momentum,
+                eps, relu, residual)[0];
 }
 
 torch::Tensor linear_autograd(torch::Tensor x, torch::Tensor w,

@@ -25,6 +25,12 @@ torch::Tensor attention_autograd(torch::Tensor qkv, int64_t heads,
                                  const std::string& matrix);
 torch::Tensor layer_norm_autograd(torch::Tensor x, torch::Tensor weight,
                                   torch::Tensor bias, double eps);
+torch::Tensor batch_norm_act_autograd(
+    torch::Tensor x, torch::Tensor weight, torch::Tensor bias,
+    torch::Tensor running_mean, torch::Tensor running_var,
+    c10::optional<torch::Tensor> residual, bool relu, bool training,
+    double momentum, double eps,
+    c10::optional<torch::Tensor> num_batches_tracked);
 std::vector<torch::Tensor> add_layer_norm_autograd(torch::Tensor x,
                                                    torch::Tensor residual,
                                                    torch::Tensor weight,
@@ -314,6 +320,37 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dbeta") = c10::nullopt);
   m.def("ln_grid_cap", &mi355x::ln_grid_cap);
   m.def(
+      "bn_fwd",
+      [](torch::Tensor x, torch::Tensor weight, torch::Tensor bias,
+         torch::Tensor running_mean, torch::Tensor running_var, bool training,
+         double momentum, double eps, bool relu,
+         c10::optional<torch::Tensor> residual,
+         c10::optional<torch::Tensor> num_batches_tracked,
+         c10::optional<torch::Tensor> z,
+         c10::optional<torch::Tensor> col_stats) {
+        auto outs = mi355x::bn_fwd(x, weight, bias, running_mean, running_var,
+                                   training, momentum, eps, relu, residual,
+                                   num_batches_tracked, z, col_stats);
+        return py::make_tuple(outs[0],
+                              training ? py::cast(outs[1]) : py::none());
+      },
+      py::arg("x"), py::arg("weight"), py::arg("bias"),
+      py::arg("running_mean"), py::arg("running_var"),
+      py::arg("training") = true, py::arg("momentum") = 0.1,
+      py::arg("eps") = 1e-5, py::arg("relu") = false,
+      py::arg("residual") = c10::nullopt,
+      py::arg("num_batches_tracked") = c10::nullopt,
+      py::arg("z") = c10::nullopt, py::arg("col_stats") = c10::nullopt);
+  m.def("bn_bwd", &mi355x::bn_bwd, py::arg("dz"), py::arg("x"),
+        py::arg("col_stats"), py::arg("weight"), py::arg("z") = c10::nullopt,
+        py::arg("add") = false, py::arg("dx") = c10::nullopt,
+        py::arg("dresidual") = c10::nullopt, py::arg("dgamma") = c10::nullopt,
+        py::arg("dbeta") = c10::nullopt);
+  m.def("bn_plan", [](int64_t R, int64_t C) {
+    const auto p = mi355x::bn_plan(R, C);
+    return py::make_tuple(p[0], p[1], p[2]);
+  });
+  m.def(
       "gemm_nt",
       [](torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> bias,
          bool gelu, c10::optional<torch::Tensor> y,
@@ -503,6 +540,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("heads"), py::arg("matrix") = "f32");
   m.def("layer_norm_autograd", &mi355x::layer_norm_autograd, py::arg("x"),
         py::arg("weight"), py::arg("bias"), py::arg("eps"));
+  m.def("batch_norm_act_autograd", &mi355x::batch_norm_act_autograd,
+        py::arg("x"), py::arg("weight"), py::arg("bias"),
+        py::arg("running_mean"), py::arg("running_var"),
+        py::arg("residual") = c10::nullopt, py::arg("relu") = false,
+        py::arg("training") = true, py::arg("momentum") = 0.1,
+        py::arg("eps") = 1e-5, py::arg("num_batches_tracked") = c10::nullopt);
   m.def("add_layer_norm_autograd", &mi355x::add_layer_norm_autograd,
         py::arg("x"), py::arg("residual"), py::arg("weight"), py::arg("bias"),
         py::arg("eps"));

@@ -3,8 +3,9 @@
 // (toy_fused_fwd_bwd, toy_multistep*) toy_kernels.hip, and for the
 // flat-bucket optimizers optim_kernels.hip, for the fused self-attention
 // attention_kernels.hip, for the fused LayerNorm layernorm_kernels.hip, for
-// the tiled GEMMs gemm_kernels.hip, for the class-index cross-entropy
-// loss_kernels.hip; bound to Python in bindings.hip.
+// the fused BatchNorm batchnorm_kernels.hip, for the tiled GEMMs
+// gemm_kernels.hip, for the class-index cross-entropy loss_kernels.hip; bound
+// to Python in bindings.hip.
 #pragma once
 #include <torch/extension.h>
 #include <cstdint>
@@ -111,6 +112,43 @@ std::vector<torch::Tensor> ln_bwd(
     c10::optional<torch::Tensor> dgamma = c10::nullopt,
     c10::optional<torch::Tensor> dbeta = c10::nullopt);
 int64_t ln_grid_cap();
+
+// Fused BatchNorm, optionally with ReLU, optionally with a residual add in
+// front of the ReLU (batchnorm_kernels.hip): z = act(bn(x) + residual) over
+// the rows of a channels-last activation. x, residual, z, dz, dx, dresidual
+// are 2-D [R, C] (R = N*H*W pixels, C channels contiguous), contiguous,
+// 16-byte aligned, f32 or bf16 alike; weight, bias, the running statistics,
+// col_stats [2, C] = (mean row, rstd row), dgamma and dbeta are f32 whatever
+// the storage; arithmetic is f32. C % 4 == 0, 4 <= C <= 4096; R >= 2 in
+// training, R >= 1 in evaluation; a residual only with relu; momentum in
+// [0, 1], eps >= 0. Anything else is refused before a launch.
+// bn_fwd, training: returns (z, col_stats), updates running_mean/running_var
+//   in place (unbiased variance) and adds one to num_batches_tracked (int64,
+//   one element) on the device. Evaluation: returns (z) from the running
+//   statistics and changes nothing.
+// bn_bwd returns (dx, dgamma, dbeta) or, with add, (dx, dgamma, dbeta,
+//   dresidual). With z, the forward's OUTPUT, the gradient first passes the
+//   ReLU: g = dz * (z > 0); dresidual = g. Statistics and parameter gradients
+//   are reduced without atomics in an order fixed by the shape: reproducible.
+// Results may be preallocated.
+// bn_plan: (LC, slabs, GR), the lanes along the channels, the column slabs
+//   and the workgroups along the rows, a function of (R, C) alone.
+std::vector<torch::Tensor> bn_fwd(
+    torch::Tensor x, torch::Tensor weight, torch::Tensor bias,
+    torch::Tensor running_mean, torch::Tensor running_var, bool training,
+    double momentum, double eps, bool relu,
+    c10::optional<torch::Tensor> residual = c10::nullopt,
+    c10::optional<torch::Tensor> num_batches_tracked = c10::nullopt,
+    c10::optional<torch::Tensor> z = c10::nullopt,
+    c10::optional<torch::Tensor> col_stats = c10::nullopt);
+std::vector<torch::Tensor> bn_bwd(
+    torch::Tensor dz, torch::Tensor x, torch::Tensor col_stats,
+    torch::Tensor weight, c10::optional<torch::Tensor> z = c10::nullopt,
+    bool add = false, c10::optional<torch::Tensor> dx = c10::nullopt,
+    c10::optional<torch::Tensor> dresidual = c10::nullopt,
+    c10::optional<torch::Tensor> dgamma = c10::nullopt,
+    c10::optional<torch::Tensor> dbeta = c10::nullopt);
+std::vector<int64_t> bn_plan(int64_t R, int64_t C);
 
 // LDS-tiled MFMA GEMMs for transformer-sized linears with the MLP's
 // elementwise work in their epilogues (gemm_kernels.hip). Operands are 2-D,

@@ -21,6 +21,7 @@ ext = CUDAExtension(
         "mi355x_ddp/ops/csrc/optim_kernels.hip",
         "mi355x_ddp/ops/csrc/attention_kernels.hip",
         "mi355x_ddp/ops/csrc/layernorm_kernels.hip",
+        "mi355x_ddp/ops/csrc/batchnorm_kernels.hip",
         "mi355x_ddp/ops/csrc/gemm_kernels.hip",
         "mi355x_ddp/ops/csrc/loss_kernels.hip",
         "mi355x_ddp/ops/csrc/rccl_comm.hip",
