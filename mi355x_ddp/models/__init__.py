@@ -6,3 +6,4 @@ from .attention import HipSelfAttention  # noqa: F401
 from .layernorm import HipLayerNorm  # noqa: F401
 from .mlp import HipMlp  # noqa: F401
 from .batchnorm import HipBatchNorm2d  # noqa: F401
+from .conv import HipConv2d  # noqa: F401

@@ -3,11 +3,9 @@ environment — SURVEY §7 environment facts).
 
 The profiling entrypoint (reference multigpu_profile.py:14,25 imports
 torchvision's resnet50) needs a real convolutional workload whose DDP
-gradient payload is ~102 MB across many buckets. Conv/BN/pool
-run through MIOpen via PyTorch-ROCm (SURVEY §2.2 N11 — re-writing ~50 conv
-shapes by hand is out of scope; the profile stage's purpose is trace
-capture and multi-bucket reduction); the final FC layer uses the
-hand-written MFMA linear.
+gradient payload is ~102 MB across many buckets. By default
+conv/BN/pool run through MIOpen via PyTorch-ROCm; the
+final FC layer uses the hand-written MFMA linear.
 
 Standard bottleneck architecture (He et al. 2015), v1.5 variant (stride on
 the 3x3 conv) to match what torchvision's resnet50 computes.
@@ -17,6 +15,14 @@ the 3x3 conv) to match what torchvision's resnet50 computes.
 buffer names: the ReLUs after the stem's and a block's first two norms ride in
 the norm's kernels, a block's last norm also takes the residual add and the
 final ReLU, and the downsample norm runs without activation.
+
+`conv="hip"` (opt-in; the default "torch" is nn.Conv2d, untouched) puts
+`HipConv2d` in the place of the 52 1x1 and 3x3 convolutions, under the same
+parameter names: one implicit-GEMM MFMA kernel family (`ops.conv2d`) serves
+them all, forward and backward, since every one has channels that are
+multiples of 64, stride 1 or 2 and padding k//2. The 7x7 stem (3 input
+channels) and the two poolings stay with the library. The switch is
+independent of `norm`; state dicts interchange between all four combinations.
 """
 
 from __future__ import annotations
@@ -25,15 +31,27 @@ import torch
 from torch import nn
 
 from .batchnorm import HipBatchNorm2d
+from .conv import HipConv2d
 from .toy import HipLinear
 
 
-def conv3x3(cin: int, cout: int, stride: int = 1) -> nn.Conv2d:
-    return nn.Conv2d(cin, cout, 3, stride=stride, padding=1, bias=False)
+def _conv(conv: str, cin: int, cout: int, k: int, stride: int) -> nn.Module:
+    if conv == "hip":
+        return HipConv2d(cin, cout, k, stride)
+    if conv == "torch":
+        return nn.Conv2d(cin, cout, k, stride=stride, padding=k // 2,
+                         bias=False)
+    raise ValueError(f"conv must be 'torch' or 'hip', got {conv!r}")
 
 
-def conv1x1(cin: int, cout: int, stride: int = 1) -> nn.Conv2d:
-    return nn.Conv2d(cin, cout, 1, stride=stride, bias=False)
+def conv3x3(cin: int, cout: int, stride: int = 1,
+            conv: str = "torch") -> nn.Module:
+    return _conv(conv, cin, cout, 3, stride)
+
+
+def conv1x1(cin: int, cout: int, stride: int = 1,
+            conv: str = "torch") -> nn.Module:
+    return _conv(conv, cin, cout, 1, stride)
 
 
 def _norm(norm: str, channels: int, act: str) -> nn.Module:
@@ -49,14 +67,15 @@ class Bottleneck(nn.Module):
     expansion = 4
 
     def __init__(self, cin: int, width: int, stride: int = 1,
-                 downsample: nn.Module = None, norm: str = "torch"):
+                 downsample: nn.Module = None, norm: str = "torch",
+                 conv: str = "torch"):
         super().__init__()
         self.norm = norm
-        self.conv1 = conv1x1(cin, width)
+        self.conv1 = conv1x1(cin, width, conv=conv)
         self.bn1 = _norm(norm, width, "relu")
-        self.conv2 = conv3x3(width, width, stride)
+        self.conv2 = conv3x3(width, width, stride, conv=conv)
         self.bn2 = _norm(norm, width, "relu")
-        self.conv3 = conv1x1(width, width * self.expansion)
+        self.conv3 = conv1x1(width, width * self.expansion, conv=conv)
         self.bn3 = _norm(norm, width * self.expansion, "relu")
         self.relu = nn.ReLU(inplace=True)
         self.downsample = downsample
@@ -78,10 +97,11 @@ class Bottleneck(nn.Module):
 
 
 class ResNet(nn.Module):
-    def __init__(self, layers, num_classes: int = 1000, norm: str = "torch"):
+    def __init__(self, layers, num_classes: int = 1000, norm: str = "torch",
+                 conv: str = "torch"):
         super().__init__()
         self.inplanes = 64
-        self.norm = norm
+        self.norm, self.conv = norm, conv
         self.conv1 = nn.Conv2d(3, 64, 7, stride=2, padding=3, bias=False)
         self.bn1 = _norm(norm, 64, "relu")
         self.relu = nn.ReLU(inplace=True)
@@ -93,7 +113,7 @@ class ResNet(nn.Module):
         self.avgpool = nn.AdaptiveAvgPool2d((1, 1))
         self.fc = HipLinear(512 * Bottleneck.expansion, num_classes)
         for m in self.modules():
-            if isinstance(m, nn.Conv2d):
+            if isinstance(m, (nn.Conv2d, HipConv2d)):
                 nn.init.kaiming_normal_(m.weight, mode="fan_out",
                                         nonlinearity="relu")
             elif isinstance(m, nn.BatchNorm2d):
@@ -104,12 +124,13 @@ class ResNet(nn.Module):
         downsample = None
         cout = width * Bottleneck.expansion
         if stride != 1 or self.inplanes != cout:
-            downsample = nn.Sequential(conv1x1(self.inplanes, cout, stride),
-                                       _norm(self.norm, cout, "none"))
+            downsample = nn.Sequential(
+                conv1x1(self.inplanes, cout, stride, self.conv),
+                _norm(self.norm, cout, "none"))
         layers = [Bottleneck(self.inplanes, width, stride, downsample,
-                             self.norm)]
+                             self.norm, self.conv)]
         self.inplanes = cout
-        layers += [Bottleneck(cout, width, norm=self.norm)
+        layers += [Bottleneck(cout, width, norm=self.norm, conv=self.conv)
                    for _ in range(1, blocks)]
         return nn.Sequential(*layers)
 
@@ -124,5 +145,6 @@ class ResNet(nn.Module):
         return self.fc(x)
 
 
-def resnet50(num_classes: int = 1000, norm: str = "torch") -> ResNet:
-    return ResNet([3, 4, 6, 3], num_classes, norm)
+def resnet50(num_classes: int = 1000, norm: str = "torch",
+             conv: str = "torch") -> ResNet:
+    return ResNet([3, 4, 6, 3], num_classes, norm, conv)

@@ -293,6 +293,112 @@ def batch_norm_act(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
 
 
 # ---------------------------------------------------------------------------
+# Implicit-GEMM convolutions, 1x1 and 3x3 (csrc/conv_kernels.hip)
+# ---------------------------------------------------------------------------
+def conv_check_args(x: torch.Tensor, weight: torch.Tensor, stride: int,
+                    padding: Optional[int]) -> None:
+    """Every rule of `conv2d`, ahead of any launch; raises ValueError. The
+    rules hold on either device, except that the CPU path also takes dtypes
+    other than fp32 and bf16 (it serves the fp64 references) and has no
+    alignment rule."""
+    who = "conv2d"
+    if x.dim() != 4 or weight.dim() != 4:
+        raise ValueError(f"{who}: x must be [N, Cin, H, W] and weight "
+                         f"[Cout, Cin, k, k], got {tuple(x.shape)} and "
+                         f"{tuple(weight.shape)}")
+    cout, cin, k, k2 = weight.shape
+    if k != k2 or k not in (1, 3):
+        raise ValueError(f"{who}: kernel size must be 1x1 or 3x3, got "
+                         f"{k}x{k2}")
+    if padding is not None and padding != k // 2:
+        raise ValueError(f"{who}: padding must be k//2 = {k // 2}, got "
+                         f"{padding}")
+    if stride not in (1, 2):
+        raise ValueError(f"{who}: stride must be 1 or 2, got {stride}")
+    if x.shape[1] != cin:
+        raise ValueError(f"{who}: x has {x.shape[1]} channels, weight takes "
+                         f"{cin} (groups are not supported)")
+    if cin % 16 or cout % 16 or cin == 0 or cout == 0:
+        raise ValueError(f"{who}: Cin and Cout must be multiples of 16, got "
+                         f"{cin} and {cout}")
+    dt = _conv_dtype(x)  # under autocast both operands are cast to it
+    if (dt or x.dtype) != (dt or weight.dtype) or x.device != weight.device:
+        raise ValueError(f"{who}: x is {x.dtype} on {x.device}, weight "
+                         f"{weight.dtype} on {weight.device}")
+    n, _, h, w = x.shape
+    if h < 1 or w < 1 or n * h * w >= 2 ** 31:
+        raise ValueError(f"{who}: H, W >= 1 and N*H*W < 2^31, got "
+                         f"{tuple(x.shape)}")
+    if x.is_cuda:
+        if (dt or x.dtype) not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"{who}: dtype must be float32 or bfloat16, got "
+                             f"{dt or x.dtype}")
+        # only storage the kernels read in place has to be aligned: a cast,
+        # a layout change and the 3x3 packing each give a fresh allocation
+        x_view = x.dtype == (dt or x.dtype) and \
+            x.is_contiguous(memory_format=torch.channels_last)
+        w_view = k == 1 and weight.dtype == (dt or x.dtype) and \
+            weight.is_contiguous()
+        if (x_view and x.data_ptr() % 16) or \
+                (w_view and weight.data_ptr() % 16):
+            raise ValueError(f"{who}: x and weight must be 16-byte aligned "
+                             f"where they are read in place")
+
+
+def conv2d(x: torch.Tensor, weight: torch.Tensor, stride: int = 1,
+           padding: Optional[int] = None) -> torch.Tensor:
+    """F.conv2d(x, weight, None, stride, k//2) for the 1x1 and 3x3
+    convolutions of a ResNet, forward and backward on implicit-GEMM MFMA
+    kernels of our own.
+
+    `x` is [N, Cin, H, W], `weight` [Cout, Cin, k, k] with k 1 or 3, `stride`
+    1 or 2, `padding` k//2 (the default; anything else raises), no bias, no
+    groups, no dilation. Cin and Cout must be multiples of 16, the dtype fp32
+    or bf16 alike for both, N*H*W below 2^31; `conv_check_args` raises
+    ValueError for everything else before anything is launched. Under
+    autocast both operands are used in the autocast dtype (nn.Conv2d's
+    policy, as `linear` does).
+
+    On the GPU `x` is used in its channels-last form, as `batch_norm_act`
+    does: a view when it already is channels-last, otherwise ONE
+    `.contiguous(memory_format=torch.channels_last)` copy; the result is the
+    channels-last [N, Cout, Ho, Wo] view of the kernels' [N*Ho*Wo, Cout]
+    matrix, Ho = (H + 2*(k//2) - k)//stride + 1. The kernels read the weight
+    packed as [Cout, k*k, Cin]: one small copy per call (a view for k = 1),
+    folded into the autocast cast where there is one. The weight gradient is
+    stored by the kernels in `weight`'s own layout and dtype and is the same
+    bits run to run (no atomics). Nothing is read back to the host, so the
+    call and its backward can be captured into a graph; as for any captured
+    backward, `x` and `weight` must not carry an AccumulateGrad node made on
+    another stream and still held by an earlier autograd graph (fresh leaves,
+    or nothing retained from a run outside the capture: docs/KERNELS.md).
+    The CPU path is F.conv2d."""
+    conv_check_args(x, weight, stride, padding)
+    k = weight.shape[-1]
+    if not x.is_cuda:
+        return F.conv2d(x, weight, None, stride, k // 2)
+    dt = _conv_dtype(x) or x.dtype
+    cout, cin = weight.shape[:2]
+    n, _, h, w = x.shape
+    # the packed copy takes no gradient: dW goes to `weight` from the kernels
+    wp = weight.detach().permute(0, 2, 3, 1).reshape(cout, k * k, cin) \
+        .to(dt).contiguous()
+    xc = x.to(dt).contiguous(memory_format=torch.channels_last)
+    rows = xc.permute(0, 2, 3, 1).reshape(-1, cin).contiguous()
+    y = ext().conv2d_autograd(rows, weight.contiguous(), wp, n, h, w, stride)
+    ho = (h + 2 * (k // 2) - k) // stride + 1
+    wo = (w + 2 * (k // 2) - k) // stride + 1
+    return y.view(n, ho, wo, cout).permute(0, 3, 1, 2)
+
+
+def _conv_dtype(x):
+    """The autocast dtype where the convolution is cast to one, else None."""
+    if x.is_cuda and torch.is_autocast_enabled("cuda"):
+        return torch.get_autocast_dtype("cuda")
+    return None
+
+
+# ---------------------------------------------------------------------------
 # Losses (reference: CE at single_gpu.py:24, MSE at multinode_torchrun.py:46;
 # both take float probability/value targets of the same shape as the output)
 # ---------------------------------------------------------------------------

@@ -350,7 +350,58 @@ struct MlpFn : public torch::autograd::Function<MlpFn> {
   }
 };
 
+// y = conv2d(x, weight) on the implicit-GEMM kernels. `x` is the 2-D
+// channels-last matrix, `weight` the parameter [Cout, Cin, k, k] (or its
+// autocast copy) that receives the gradient, `wp` the same values packed as
+// [Cout, k*k, Cin], which the kernels read; it takes no gradient. Saved: x
+// and wp. dW is stored in weight's layout and dtype by the kernels.
+struct Conv2dFn : public torch::autograd::Function<Conv2dFn> {
+  static torch::Tensor forward(AutogradContext* ctx, torch::Tensor x,
+                               torch::Tensor weight, torch::Tensor wp,
+                               int64_t N, int64_t H, int64_t W,
+                               int64_t stride) {
+    TORCH_CHECK(weight.dim() == 4 && wp.dim() == 3 &&
+                    weight.size(0) == wp.size(0) &&
+                    weight.size(1) == wp.size(2) &&
+                    weight.size(2) * weight.size(3) == wp.size(1) &&
+                    weight.size(2) == weight.size(3),
+                "conv2d_autograd: wp must be weight packed as "
+                "[Cout, k*k, Cin]");
+    auto y = conv2d_fwd(x, wp, N, H, W, stride);
+    ctx->save_for_backward({x, wp});
+    ctx->saved_data["dims"] = std::vector<int64_t>{N, H, W, stride,
+                                                   weight.size(2)};
+    ctx->saved_data["bf16"] = weight.scalar_type() == at::kBFloat16;
+    return y;
+  }
+
+  static variable_list backward(AutogradContext* ctx, variable_list grads) {
+    auto saved = ctx->get_saved_variables();
+    const auto &x = saved[0], &wp = saved[1];
+    const auto d = ctx->saved_data["dims"].toIntVector();
+    auto dy = grads[0].contiguous();
+    torch::Tensor dx, dw;
+    if (ctx->needs_input_grad(0))
+      dx = conv2d_bwd_input(dy, wp, d[0], d[1], d[2], d[3]);
+    if (ctx->needs_input_grad(1)) {
+      dw = torch::empty(
+          {wp.size(0), wp.size(2), d[4], d[4]},
+          wp.options().dtype(ctx->saved_data["bf16"].toBool() ? at::kBFloat16
+                                                              : at::kFloat));
+      conv2d_bwd_weight(dy, x, d[0], d[1], d[2], d[4], d[3], dw);
+    }
+    return {dx, dw, torch::Tensor(), torch::Tensor(), torch::Tensor(),
+            torch::Tensor(), torch::Tensor()};
+  }
+};
+
 }  // namespace
+
+torch::Tensor conv2d_autograd(torch::Tensor x, torch::Tensor weight,
+                              torch::Tensor wp, int64_t N, int64_t H,
+                              int64_t W, int64_t stride) {
+  return Conv2dFn::apply(x, weight, wp, N, H, W, stride);
+}
 
 torch::Tensor mlp_autograd(torch::Tensor x, torch::Tensor w1, torch::Tensor b1,
                            torch::Tensor w2, torch::Tensor b2) {

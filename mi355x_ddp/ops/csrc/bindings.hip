@@ -38,6 +38,9 @@ std::vector<torch::Tensor> add_layer_norm_autograd(torch::Tensor x,
                                                    double eps);
 torch::Tensor mlp_autograd(torch::Tensor x, torch::Tensor w1, torch::Tensor b1,
                            torch::Tensor w2, torch::Tensor b2);
+torch::Tensor conv2d_autograd(torch::Tensor x, torch::Tensor weight,
+                              torch::Tensor wp, int64_t N, int64_t H,
+                              int64_t W, int64_t stride);
 torch::Tensor linear_gelu_autograd(torch::Tensor x, torch::Tensor w,
                                    torch::Tensor b);
 
@@ -549,6 +552,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("add_layer_norm_autograd", &mi355x::add_layer_norm_autograd,
         py::arg("x"), py::arg("residual"), py::arg("weight"), py::arg("bias"),
         py::arg("eps"));
+  m.def("conv2d_fwd", &mi355x::conv2d_fwd, py::arg("x"), py::arg("wp"),
+        py::arg("N"), py::arg("H"), py::arg("W"), py::arg("stride"));
+  m.def("conv2d_bwd_input", &mi355x::conv2d_bwd_input, py::arg("dy"),
+        py::arg("wp"), py::arg("N"), py::arg("H"), py::arg("W"),
+        py::arg("stride"));
+  m.def("conv2d_bwd_weight", &mi355x::conv2d_bwd_weight, py::arg("dy"),
+        py::arg("x"), py::arg("N"), py::arg("H"), py::arg("W"), py::arg("k"),
+        py::arg("stride"), py::arg("dw") = c10::nullopt);
+  m.def("conv_wgrad_plan",
+        [](int64_t M, int64_t Cout, int64_t Cin, int64_t taps) {
+          const auto p = mi355x::conv_wgrad_plan(M, Cout, Cin, taps);
+          return py::make_tuple(p[0], p[1], p[2], p[3]);
+        },
+        py::arg("M"), py::arg("Cout"), py::arg("Cin"), py::arg("taps"));
+  m.def("conv2d_autograd", &mi355x::conv2d_autograd, py::arg("x"),
+        py::arg("weight"), py::arg("wp"), py::arg("N"), py::arg("H"),
+        py::arg("W"), py::arg("stride"));
   m.def("mlp_autograd", &mi355x::mlp_autograd, py::arg("x"), py::arg("w1"),
         py::arg("b1"), py::arg("w2"), py::arg("b2"));
   m.def("linear_gelu_autograd", &mi355x::linear_gelu_autograd, py::arg("x"),

@@ -4,8 +4,9 @@
 // flat-bucket optimizers optim_kernels.hip, for the fused self-attention
 // attention_kernels.hip, for the fused LayerNorm layernorm_kernels.hip, for
 // the fused BatchNorm batchnorm_kernels.hip, for the tiled GEMMs
-// gemm_kernels.hip, for the class-index cross-entropy loss_kernels.hip; bound
-// to Python in bindings.hip.
+// gemm_kernels.hip, for the implicit-GEMM convolutions conv_kernels.hip, for
+// the class-index cross-entropy loss_kernels.hip; bound to Python in
+// bindings.hip.
 #pragma once
 #include <torch/extension.h>
 #include <cstdint>
@@ -180,6 +181,36 @@ std::vector<torch::Tensor> gemm_tn(
     c10::optional<torch::Tensor> db = c10::nullopt);
 std::vector<int64_t> gemm_tile_shape();
 torch::Tensor gelu_grad_mul(torch::Tensor da, torch::Tensor h);
+
+// Implicit-GEMM convolutions for a channels-last ResNet (conv_kernels.hip):
+// kernel size k in {1, 3}, padding k/2, stride 1 or 2, no bias, groups or
+// dilation. x is [N*H*W, Cin], y and dy are [M, Cout] with M = N*Ho*Wo and
+// Ho = (H + 2*(k/2) - k)/stride + 1: the 2-D channels-last matrices. wp is
+// the weight PACKED as [Cout, k*k, Cin]. All of them contiguous, 16-byte
+// aligned, f32 or bf16 alike; Cin and Cout multiples of 16; N*H*W < 2^31,
+// N >= 0, H, W >= 1. Anything else is refused before a launch; N == 0
+// launches none of our kernels (y and dx are empty, and the one thing that
+// runs is torch's fill of dw with zeros, the sum over no pixels).
+// Accumulation is f32 with one rounding on the store.
+// conv2d_fwd returns y; conv2d_bwd_input returns dx [N*H*W, Cin], every row
+//   stored once (the untouched rows of a strided 1x1 as zeros).
+// conv2d_bwd_weight returns dw in the PARAMETER's layout [Cout, Cin, k, k];
+//   a preallocated dw may be f32 or bf16 whatever the operands' dtype. The
+//   sum over the M output pixels is split into GS slices whose f32 tiles go
+//   through a workspace [GS, Cout, k*k, Cin] and are added in slice order: no
+//   atomics, the same bits run to run.
+// conv_wgrad_plan: (tile rows, tile columns, GS, rows per slice), a function
+//   of (M, Cout, Cin, taps = k*k) alone.
+torch::Tensor conv2d_fwd(torch::Tensor x, torch::Tensor wp, int64_t N,
+                         int64_t H, int64_t W, int64_t stride);
+torch::Tensor conv2d_bwd_input(torch::Tensor dy, torch::Tensor wp, int64_t N,
+                               int64_t H, int64_t W, int64_t stride);
+torch::Tensor conv2d_bwd_weight(torch::Tensor dy, torch::Tensor x, int64_t N,
+                                int64_t H, int64_t W, int64_t k,
+                                int64_t stride,
+                                c10::optional<torch::Tensor> dw = c10::nullopt);
+std::vector<int64_t> conv_wgrad_plan(int64_t M, int64_t Cout, int64_t Cin,
+                                     int64_t taps);
 
 // Cross-entropy with class-probability targets (C may be 1: the reference's
 // degenerate Linear(20,1) case, single_gpu.py:24 + utils.py:7).

@@ -23,6 +23,7 @@ ext = CUDAExtension(
         "mi355x_ddp/ops/csrc/layernorm_kernels.hip",
         "mi355x_ddp/ops/csrc/batchnorm_kernels.hip",
         "mi355x_ddp/ops/csrc/gemm_kernels.hip",
+        "mi355x_ddp/ops/csrc/conv_kernels.hip",
         "mi355x_ddp/ops/csrc/loss_kernels.hip",
         "mi355x_ddp/ops/csrc/rccl_comm.hip",
         "mi355x_ddp/ops/csrc/p2p_mesh.hip",
